@@ -1,12 +1,22 @@
 #!/usr/bin/env python3
 """Benchmark of the particle hot path on MI355X: particle-updates/sec + achieved HBM GB/s (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME] [--scaling weak|strong|both]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME] [--dump-outputs DIR] [--full]
 
 A "step" is one simulated frame (one pass of the hot path: per-frame inputs upload, init where the frame spawns, update +
 kill + list maintenance, ribbon sort where the layout has RIBBON_ID) over particle state resident in HBM. After W warm-up
-frames the script times WINDOWS (default 25) windows of exactly K steps each, every one bracketed by a barrier and a device
+frames the script times WINDOWS windows of exactly K steps each, every one bracketed by a barrier and a device
 synchronisation; `ms_per_step` / `value` are the MEDIAN window, the others are listed under "windows" (min, all).
+
+Plain run (the default): the headline configuration alone - set up, W warm-up frames, ONE window of exactly K timed steps, the
+outputs if --dump-outputs is given, the result line. --full adds everything else described below: 25 windows (unless --windows
+says otherwise), the other configurations (N = 1) or the strong-scaling run (N > 1), the small-effects scene, the CPU baseline,
+the parity gate, the HBM-traffic counter passes, the one-rank hnb_comm check and the complete record (--full-json).
+
+--dump-outputs DIR: after the timed steps, what the headline configuration's last step left for a caller - every stored attribute
+plane, the alive list and the alive count of every effect - as DIR/<name>.npy (float32; integer words as float64, exactly), a fixed
+seeded sample of rows where the whole would exceed 64 MB. The inputs depend on the arguments alone, so two builds run with the same
+arguments can be compared file for file.
 
 Configurations (synthetic scalings of the reference's example assets):
   c2 (default, the headline)  examples/firework.rs `trails` effect, capacity 16,777,216 per GPU, burst spawn during warm-up,
@@ -33,9 +43,9 @@ Configurations (synthetic scalings of the reference's example as
                               4096 instances at N = 8 (`--instances 4096` puts the whole configuration on one GPU);
   c5                          examples/ribbon.rs, capacity 4,194,304 per GPU, rate spawner in steady spawn/kill churn,
                               ribbon sort included in the step.
-At N = 1 the default command runs c2 as the JSON line and appends the others under "configs".
+At N = 1 `--full` runs c2 as the JSON line and appends the others under "configs".
 
-Roofline (every configuration): the dominant kernel's HBM-side traffic is MEASURED in this run - the script re-runs itself
+Roofline (every configuration): with --full the dominant kernel's HBM-side traffic is MEASURED in this run - the script re-runs itself
 twice under `rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE` (separate passes; FETCH_SIZE doubled as
 guides/MI355X_MICROARCH.md prescribes for gfx950), cutting the dispatch list at marker kernels - and
     roofline.achieved = measured bytes per launch / the kernel's average duration (HIP events, this process),
@@ -43,10 +53,10 @@ guides/MI355X_MICROARCH.md prescribes for gfx950), cutting the dispatch list at 
     roofline.algorithmic = SURVEY.md §8(d)'s bytes per update (68 B for the firework) x updates / the same time: what the
                         launch is WORTH, which exceeds what it moves where the design elides traffic (age cohorts,
                         lifetime culling, no list traffic in frames without casualties).
-Without rocprofv3 the committed profiles/traffic.json is used if its kernel-source stamp matches this tree, else the
+Without rocprofv3 (and in a plain run) the committed profiles/traffic.json is used if its kernel-source stamp matches this tree, else the
 fraction falls back to a stated per-configuration byte model (`traffic_source` says which).
 
-Parity gate (BASELINE.md §3 "same run"): before a configuration's number is accepted, the state its timed frames produced is compared bit
+Parity gate (--full; BASELINE.md §3 "same run"): before a configuration's number is accepted, the state its timed frames produced is compared bit
 for bit with the CPU oracle (oracle/, the restatement of the reference's WGSL semantics): burst configurations (c2, c2_interop, c3, c4) on one
 slab of slots of the FULL-SIZE effect after all timed frames (a burst fills slot i with PRNG stream i: the slab IS a small effect with that
 slot_base); churn configurations (c2_mixed, c2_dieoff, c2_events, c5) by replaying the same regime (same dt, warm-up and frame count) at a reduced
@@ -57,8 +67,8 @@ seconds per configuration). The line carries "parity": {"checked": [...], "ok": 
 the exit code is 1.
 
 Output: the LAST stdout line is the short result (<= 4 KB: the c2 headline with roofline, cpu_baseline, parity and a one-row summary of every
-other configuration); the complete record (every window, stage, counter and per-kernel figure) goes to profiles/bench_full.json (and
-gpurun_out/bench_full.json when that directory exists) and to stderr.
+other configuration); with --full the complete record (every window, stage, counter and per-kernel figure) goes to --full-json (default
+profiles/bench_full.json) and to stderr.
 
 N > 1: `python bench.py --gpus N` launches itself under `python -m torch.distributed.run` (one process per GPU, RCCL); when the
 driver already started it that way (WORLD_SIZE in the environment) it just runs its rank. There is no data-path collective: the
@@ -782,6 +792,46 @@ def warmup_frames(name, requested):
     return requested
 
 
+DUMP_BUDGET_BYTES = 60 << 20   # --dump-outputs: under 64 MB in all
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(w, out_dir):
+    """--dump-outputs: what a caller of the timed path receives after its last step - every stored attribute plane, the alive list and
+    the alive count of every effect - as out_dir/<name>.npy. Float planes stay float32; integer words (packed colours, list entries) become
+    float64, which holds every u32 exactly. Where the whole would exceed DUMP_BUDGET_BYTES, every effect contributes the same fixed, seeded
+    sample of rows (rows.npy: slot indices of the attribute planes, row indices of the alive list, -1 past the alive count). Effects of one
+    asset are concatenated (c4's instances); effects of different assets (c2_events) get a prefix fx<i>_."""
+    from bevy_hanabi_amd import runtime
+    os.makedirs(out_dir, exist_ok=True)
+    per_fx = []
+    for i, fx in enumerate(w.fxs):
+        asset = w.assets[i] if len(w.assets) == len(w.fxs) else w.assets[0]
+        per_fx.append((fx, _stored_attrs(asset)))
+    row_bytes = [16 + sum(runtime.ATTR_COMPONENTS[a.id] * (4 if runtime.ATTR_IS_FLOAT[a.id] else 8) for a in attrs) for _fx, attrs in per_fx]
+    total = sum(fx.capacity * b for (fx, _), b in zip(per_fx, row_bytes))
+    frac = min(1.0, DUMP_BUDGET_BYTES / max(total, 1))
+    out = {}
+    for i, (fx, attrs) in enumerate(per_fx):
+        cap = fx.capacity
+        n = max(1, int(cap * frac))
+        rows = np.arange(cap) if n >= cap else np.sort(np.random.default_rng(DUMP_SEED).choice(cap, n, replace=False))
+        arrays = {"rows": rows.astype(np.float64), "alive_count": np.array([fx.alive_count()], np.float64)}
+        for a in attrs:
+            plane = fx.read_attr(a.id)[rows]
+            arrays[a.name] = plane if plane.dtype == np.float32 else plane.astype(np.float64)
+        alive = fx.alive_list()
+        arrays["alive_list"] = np.full(len(rows), -1.0)
+        listed = rows < len(alive)
+        arrays["alive_list"][listed] = alive[rows[listed]]
+        prefix = "" if len(w.assets) == 1 else f"fx{i}_"
+        for k, v in arrays.items():
+            out.setdefault(prefix + k, []).append(v)
+    for k, parts in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.concatenate(parts))
+    return sorted(out)
+
+
 def run_config(name, args, D, strong=False, pmc=None):
     """Runs one configuration on this rank; returns the result dict on rank 0 (None elsewhere).
     pmc: None (normal run) or a dict {"begin": tag, "end": tag}: the short run a rocprofv3 counter pass wraps - marker kernels
@@ -897,6 +947,9 @@ def run_config(name, args, D, strong=False, pmc=None):
         timing["init_ms_avg"] = sum(v["init_ms_avg"] for v in per_program.values())
         timing["compact_ms_avg"] = sum(v["compact_ms_avg"] for v in per_program.values())
     ctx.enable_kernel_timing(0)
+    if getattr(args, "dump_outputs", None) and name == args.config and not strong:
+        dump_dir = args.dump_outputs if D.rank == 0 else os.path.join(args.dump_outputs, f"rank{D.rank}")
+        print(f"bench: outputs of the last timed step -> {dump_dir}: {', '.join(dump_outputs(w, dump_dir))}", file=sys.stderr)
     if name == "c2_dieoff":
         ts = w.dieoff_timing
         tot = sum(t["frames"] for t in ts) or 1
@@ -1123,7 +1176,7 @@ def measure_traffic(args, names):
             outdir = os.path.join(tmp, counter)
             # (DURATION: a third pass with the kernel trace alone - counter collection perturbs the durations it would report)
             cmd = [exe, "--kernel-trace"] + (["--pmc", counter] if counter != "DURATION" else []) + ["--output-format", "csv", "-d", outdir, "--", sys.executable, os.path.abspath(__file__),
-                   "--pmc-child", "--pmc-configs", ",".join(names), "--config", args.config]
+                   "--pmc-child", "--pmc-configs", ",".join(names), "--config", args.config, "--full"]   # (--full: the window count, hence dt, of the timed run)
             if args.capacity:
                 cmd += ["--capacity", str(args.capacity)]
             if args.instances:
@@ -1281,20 +1334,41 @@ def threads_launch(args):
     return 0
 
 
+def apply_run_mode(args):
+    """A plain run (no --full) does what the headline figure needs and nothing else: one window, weak scaling, no other configuration, no
+    scene, CPU baseline, parity gate, counter passes, one-rank hnb_comm check or complete record (unless --full-json names one)."""
+    if args.windows is None:
+        args.windows = 25 if args.full else 1
+    if args.scaling is None:
+        args.scaling = "both" if args.full else "weak"
+    if args.full and args.full_json is None:
+        args.full_json = os.path.join(ROOT, "profiles", "bench_full.json")
+    if not args.full:
+        args.parity = args.comm = args.scene = False
+        args.no_extra_configs = args.no_cpu_baseline = True
+        args.pmc = "off"
+    return args
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--windows", type=int, default=25, help="timed windows of --steps frames each; the line reports the median window")
+    ap.add_argument("--windows", type=int, default=None, help="timed windows of --steps frames each; the line reports the median window (default: 1, with --full 25)")
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c2")
-    ap.add_argument("--scaling", choices=["weak", "strong", "both"], default="both")
+    ap.add_argument("--scaling", choices=["weak", "strong", "both"], default=None, help="N > 1 (default: weak, with --full both)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: 25 windows, the other configurations (N = 1) or the strong-scaling run (N > 1), the small-effects scene, "
+                         "the CPU baseline, the parity gate, the HBM-traffic counter passes, the one-rank hnb_comm check, the complete record")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the headline configuration's state (attribute planes, alive list, alive count) as DIR/<name>.npy")
     ap.add_argument("--capacity", type=int, default=None, help="particles per effect instance (default: the configuration's)")
     ap.add_argument("--instances", type=int, default=None, help="c4: instances per GPU (weak) / in total (strong); default 512")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", dest="parity", action="store_false", default=True,
                     help="skip the oracle comparison of the state the timed frames produced (A/B tooling only: the line then says parity.ok = null)")
-    ap.add_argument("--full-json", default=os.path.join(ROOT, "profiles", "bench_full.json"), help="where the complete record goes (the last stdout line is the short one)")
+    ap.add_argument("--full-json", default=None, help="where the complete record goes (the last stdout line is the short one; default with --full: profiles/bench_full.json)")
     ap.add_argument("--scene", dest="scene", action="store_true", default=True,
                     help="N = 1: append the small-effects scene (26 example effects in one context, tools/scene_bench.py) as \"small_effects_scene\" (default)")
     ap.add_argument("--no-scene", dest="scene", action="store_false")
@@ -1314,7 +1388,7 @@ def main():
     ap.add_argument("--comm-lib", default=None, help="N > 1 dry runs: the collective library hnb_comm_* loads instead of librccl (tests/fake_rccl/libfake_rccl.so takes several ranks on one GPU)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only for dry runs)")
     ap.add_argument("--force-device", type=int, default=None, help="dry runs: every rank uses this GPU instead of LOCAL_RANK")
-    args = ap.parse_args()
+    args = apply_run_mode(ap.parse_args())
 
     if args.launcher == "threads" and "WORLD_SIZE" not in os.environ and not args.pmc_child:
         sys.exit(threads_launch(args))
@@ -1418,15 +1492,16 @@ def main():
     rc = 0
     if D.rank == 0:
         short = short_line(out, args)
-        text = json.dumps(out)
-        for path in [args.full_json] + ([os.path.join(ROOT, "gpurun_out", "bench_full.json")] if os.path.isdir(os.path.join(ROOT, "gpurun_out")) else []):
+        if args.full_json:
+            text = json.dumps(out)
+            path = os.path.abspath(args.full_json)
             try:
                 os.makedirs(os.path.dirname(path), exist_ok=True)
                 with open(path, "w") as f:
                     f.write(text + "\n")
             except OSError as e:
                 print(f"note: could not write {path}: {e}", file=sys.stderr)
-        print(text, file=sys.stderr, flush=True)          # the complete record, for a log; stdout carries the short line LAST
+            print(text, file=sys.stderr, flush=True)      # the complete record, for a log; stdout carries the short line LAST
         # The collective library (librccl, loaded for `comm`) prints a banner and warnings through C stdio into this process's stdout: buffered there, they
         # would land BEHIND this line when the process exits (seen: "Librccl path : ..." as the last line of a run). Flush C stdio first, start on a fresh line.
         try:
@@ -1483,7 +1558,9 @@ def short_line(full, args):
         parity["timed_state"] = {"checked": sum(len(t["checks"]) for t in timed), "compared": sum(len(t["diffs"]) for t in timed), "ok": all(t["ok"] for t in timed)}
     if failed:
         parity["failed"] = {p["config"]: (p.get("problems") or ["?"])[0][:56] for p in parity_all if not p.get("ok")}
-    if not args.parity:
+    if not getattr(args, "full", True):
+        parity["skipped"] = "plain run (--full checks parity)"
+    elif not args.parity:
         parity["skipped"] = "--no-parity"
     short = {k: full.get(k) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data")}
     if parity["ok"] is False:
@@ -1543,7 +1620,7 @@ def short_line(full, args):
     if full.get("strong"):
         short["strong"] = {k: _r(v) for k, v in full["strong"].items() if k != "workload"}
     short["build"] = full.get("build")
-    short["full_record"] = os.path.relpath(args.full_json, ROOT)
+    short["full_record"] = os.path.relpath(args.full_json, ROOT) if args.full_json else None
     if errored:
         short["config_errors"] = errored
     return short

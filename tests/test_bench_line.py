@@ -105,3 +105,65 @@ def test_a_failed_parity_check_refuses_the_value():
     assert bench.short_line(bare, args)["parity"]["checked"] == []
     off = bench.short_line(bare, argparse.Namespace(parity=False, full_json=args.full_json))
     assert off["parity"]["ok"] is None and off["parity"]["skipped"] == "--no-parity"
+
+
+def _parse(*argv):
+    ap = argparse.ArgumentParser()
+    for opt in ("--windows", "--scaling", "--full-json", "--dump-outputs"):
+        ap.add_argument(opt, default=None)
+    ap.add_argument("--full", action="store_true")
+    ap.add_argument("--pmc", default="auto")
+    args = ap.parse_args(list(argv))
+    args.parity = args.comm = args.scene = True
+    args.no_extra_configs = args.no_cpu_baseline = False
+    return bench.apply_run_mode(args)
+
+
+def test_a_plain_run_times_one_window_of_the_headline_alone():
+    plain = _parse()
+    assert plain.windows == 1 and plain.scaling == "weak" and plain.full_json is None and plain.pmc == "off"
+    assert not (plain.parity or plain.comm or plain.scene) and plain.no_extra_configs and plain.no_cpu_baseline
+    full = _parse("--full")
+    assert full.windows == 25 and full.scaling == "both" and full.full_json.endswith(os.path.join("profiles", "bench_full.json")) and full.pmc == "auto"
+    assert full.parity and full.comm and full.scene and not full.no_extra_configs and not full.no_cpu_baseline
+    line = bench.short_line({"metric": "particle-updates/sec", "value": 1.0, "ms_per_step": 0.1, "parity": None}, plain)
+    assert line["parity"]["ok"] is None and line["parity"]["skipped"].startswith("plain run") and line["full_record"] is None
+
+
+def test_dump_outputs_is_a_fixed_sample_under_64_mb(tmp_path):
+    """--dump-outputs on a stand-in for the headline's 16,777,216-slot effect: float32 / float64 files, under 64 MB, the same rows every time."""
+    import types
+
+    import numpy as np
+
+    import bevy_hanabi_amd as bh
+    from bevy_hanabi_amd import effects, runtime
+
+    class Fx:
+        capacity = 1 << 24
+
+        def read_attr(self, i):
+            a = (np.arange(self.capacity * runtime.ATTR_COMPONENTS[i], dtype=np.uint32) * 7 + i).reshape(self.capacity, -1)
+            return a.view(np.float32) if runtime.ATTR_IS_FLOAT[i] else a
+
+        def alive_count(self):
+            return self.capacity - 3
+
+        def alive_list(self):
+            return np.arange(self.alive_count(), dtype=np.uint32)[::-1].copy()
+
+    w = types.SimpleNamespace(fxs=[Fx()], assets=[effects.firework_trails(1 << 24)], bh=bh)
+    names = bench.dump_outputs(w, str(tmp_path / "a"))
+    assert {"position", "velocity", "age", "lifetime", "color", "alive_list", "alive_count", "rows"} <= set(names)
+    total = 0
+    for n in names:
+        a = np.load(tmp_path / "a" / f"{n}.npy")
+        assert a.dtype in (np.float32, np.float64), (n, a.dtype)
+        total += (tmp_path / "a" / f"{n}.npy").stat().st_size
+    assert total < 64 * 10**6
+    bench.dump_outputs(w, str(tmp_path / "b"))
+    for n in names:
+        assert np.array_equal(np.load(tmp_path / "a" / f"{n}.npy"), np.load(tmp_path / "b" / f"{n}.npy")), n
+    rows, lst = np.load(tmp_path / "a" / "rows.npy"), np.load(tmp_path / "a" / "alive_list.npy")
+    assert len(rows) > 10**6 and np.all(np.diff(rows) > 0) and np.array_equal(lst, np.where(rows < Fx.capacity - 3, Fx.capacity - 4 - rows, -1))
+    assert np.load(tmp_path / "a" / "alive_count.npy").tolist() == [Fx.capacity - 3]

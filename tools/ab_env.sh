@@ -6,8 +6,8 @@ out=${1:-gpurun_out/ab_env.log}; : > $out
 SET=${SET:-HIP_FORCE_DEV_KERNARG=1}
 one() { # label env...
   label=$1; shift
-  env "$@" timeout 300 python bench.py --config $CFG --steps 20 --no-parity --pmc off --no-cpu-baseline --no-scene --no-comm 2>gpurun_out/ab_env_err.log | tail -1 | python -c "
-import sys, json; d = json.loads(sys.stdin.read()); f = json.load(open('gpurun_out/bench_full.json')); st = f['stages']
+  env "$@" timeout 300 python bench.py --full --config $CFG --steps 20 --no-parity --pmc off --no-cpu-baseline --no-scene --no-comm --full-json "$out.full.json" 2>"$out.err" | tail -1 | python -c "
+import sys, json; d = json.loads(sys.stdin.read()); f = json.load(open('$out.full.json')); st = f['stages']
 print('$CFG %-28s ms_per_step %.4f  min/med/max %s  init %.4f update %.4f lists %.4f' % ('$label', d['ms_per_step'], d['windows']['ms_per_step_min_median_max'], st['init_ms_avg'], st['update_ms_avg'], st['lists_ms_avg']))" >> $out 2>&1
 }
 for CFG in ${CONFIGS:-c2_mixed c5 c2_events c2}; do

@@ -1,6 +1,6 @@
 #!/bin/bash
-# copy what tools/gpu_round_check.sh <tag> left in gpurun_out/ into profiles/ under the round's names.  Usage: tools/collect_round.sh <tag> <round, e.g. r06>
-T=$1; R=$2; G=gpurun_out; P=profiles
+# copy what tools/gpu_round_check.sh <tag> left in $OUT (default round_check/) into profiles/ under the round's names.  Usage: tools/collect_round.sh <tag> <round, e.g. r06>
+T=$1; R=$2; G=${OUT:-round_check}; P=profiles
 tail -1 $G/${T}_bench.json > $P/${R}_bench.json
 cp $G/${T}_bench_full.json $P/${R}_bench_full.json; cp $G/${T}_bench_full.json $P/bench_full.json
 cp $G/${T}_traffic.json $P/traffic.json

@@ -24,7 +24,7 @@ for tag, k in (("LEAN", "c2_lean"), ("INT", "c2_interop"), ("VIEW", "c2_view"), 
     v = c[k]
     sub.update({f"R06_{tag}_MS": ms(v["ms_per_step"]), f"R06_{tag}_V": sci(v["value"]), f"R06_{tag}_F": "%.2f" % v["frac"], f"R06_{tag}_B": b3(v["B_upd"]), f"R06_{tag}_WS": "%.2f" % v["ws68"]})
 readme = open(ROOT + "/README.md").read()
-a, b = readme.index("Measured on one MI355X (`python bench.py`"), readme.index("## Layout")
+a, b = readme.index("Measured on one MI355X (`python bench.py --full`"), readme.index("## Layout")
 readme = readme[:a] + open(ROOT + "/tools/README_numbers.tmpl.md").read() + readme[b:]
 for k in sorted(sub, key=len, reverse=True): readme = readme.replace(k, sub[k])
 assert "R06_" not in readme, re.findall(r"R06_\w+", readme)
@@ -38,7 +38,7 @@ names = {"c2_lean": "c2_lean", "c2_interop": "c2_interop", "c2_view": "c2_view",
          "c2_events": "c2_events real firework.rs", "c3": "c3 force field 8.4M", "c4": "c4 512 × 65,536", "c5": "c5 ribbon 4.19M"}
 for k in ("c2_lean", "c2_interop", "c2_view", "c2_reburst", "c2_mixed", "c2_dieoff", "c2_events", "c3", "c4", "c5"):
     v = c[k]; rows.append((names[k], v["ms_per_step"], v["value"], v["kernel_ms"], v.get("kernel_ms_rocprof"), v["B_upd"], v["frac"], v["ws68"], notes[k]))
-t = "| config (1 MI355X, `python bench.py`, median of 25 windows × 30 steps) | step ms | updates/s | kernel ms (HIP events) | moved B/update | kernel frac of 8 TB/s | whole step, 68 B × updates ÷ 8 TB/s | |\n|---|---|---|---|---|---|---|---|\n"
+t = "| config (1 MI355X, `python bench.py --full`, median of 25 windows × 30 steps) | step ms | updates/s | kernel ms (HIP events) | moved B/update | kernel frac of 8 TB/s | whole step, 68 B × updates ÷ 8 TB/s | |\n|---|---|---|---|---|---|---|---|\n"
 for n, m, v, k, kr, b, f, w, note in rows:
     t += f"| {n} | {ms(m)} | {v:.3g} | {ms(k)}{' / ' + ms(kr) + ' (rocprofv3)' if kr else ''} | {b:.3g} | {f:.2f} | {w:.2f} | {note} |\n"
 sc = line["small_effects_scene"]

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Development tool: turn the two PMC passes of tools/prof_bench.sh (FETCH_SIZE and WRITE_SIZE, collected in separate
-rocprofv3 runs of the default `python bench.py --no-cpu-baseline`) into profiles/traffic.json, the file bench.py reads
+rocprofv3 runs of `python bench.py --full --no-cpu-baseline`) into profiles/traffic.json, the file bench.py reads
 `roofline.traffic` from, and copy the rows of the hot-path kernels into profiles/ as evidence.
 
 HBM bytes per launch = FETCH_SIZE x 1024 x 2 + WRITE_SIZE x 1024  (the counters are in KiB; on gfx950 FETCH_SIZE reports half of
