@@ -88,6 +88,14 @@ void launch_stream(uint32_t grid, hipStream_t stream, const SlotArgs& sa, const 
     if (sa.age_cohort) k_update_slots_stream<PROG, (WAVES > HNB_STREAM_WAVES_COHORT ? HNB_STREAM_WAVES_COHORT : WAVES), 0, true><<<grid, kBlock, 0, stream>>>(sa, inst_base, fi, ublocks, cb);
     else k_update_slots_stream<PROG, WAVES, 0, false><<<grid, kBlock, 0, stream>>>(sa, inst_base, fi, ublocks, cb);
 }
+// Several list-free frames of the program in one launch (hnb_simulate_steps; SlotArgs::fuse_steps >= 2): the FUSED instantiation of the same kernel body,
+// under the register budget of the cohort instantiations (it holds the same planes in registers, for longer).
+template <class PROG, int WAVES>
+void launch_stream_fused(uint32_t grid, hipStream_t stream, const SlotArgs& sa, const uint64_t* inst_base, const DevFrameInst* fi,
+                         const uint32_t* ublocks, const CompactBufs& cb) {
+    if (sa.age_cohort) k_update_slots_stream<PROG, (WAVES > HNB_STREAM_WAVES_COHORT ? HNB_STREAM_WAVES_COHORT : WAVES), 0, true, true><<<grid, kBlock, 0, stream>>>(sa, inst_base, fi, ublocks, cb);
+    else k_update_slots_stream<PROG, WAVES, 0, false, true><<<grid, kBlock, 0, stream>>>(sa, inst_base, fi, ublocks, cb);
+}
 #define OP_(x) (uint32_t)HNB_OP_M_##x
 typedef ProgStatic<OP_(AGE_TICK)> ProgAge;                                                        // ribbon.rs
 #ifndef HNB_AGE_KERNEL
@@ -114,10 +122,11 @@ typedef ProgStatic<OP_(AGE_TICK), OP_(CONFORM_SPHERE), OP_(CONFORM_SPHERE), OP_(
 #define HNB_STREAM_WAVES_INTERP 5
 #endif
 
-void select_stream_kernel(const Ins* code, uint32_t n, StreamLaunchFn* fn, const char** name) {
-#define TRY_(PROG, WAVES) if (PROG::matches(code, n)) { *fn = &launch_stream<PROG, WAVES>; *name = #PROG; return; }
-    TRY_(ProgNone, HNB_STREAM_WAVES)
-    if (ProgAge::matches(code, n)) { *fn = &launch_stream_age; *name = "ProgAge"; return; }   // (its general instantiation: four waves per SIMD - the age prefetch of update_stream_chunk takes 16 more registers, and one scalar plane never needs more)
+void select_stream_kernel(const Ins* code, uint32_t n, StreamLaunchFn* fn, const char** name, StreamLaunchFn* fused) {
+#define TRY_(PROG, WAVES) if (PROG::matches(code, n)) { *fn = &launch_stream<PROG, WAVES>; *fused = &launch_stream_fused<PROG, WAVES>; *name = #PROG; return; }
+    *fused = nullptr;   // (no update stream, or no pre-built sequence: such a program runs single frames inside hnb_simulate_steps)
+    if (ProgNone::matches(code, n)) { *fn = &launch_stream<ProgNone, HNB_STREAM_WAVES>; *name = "ProgNone"; return; }
+    if (ProgAge::matches(code, n)) { *fn = &launch_stream_age; *fused = &launch_stream_fused<ProgAge, 4>; *name = "ProgAge"; return; }   // (its general instantiation: four waves per SIMD - the age prefetch of update_stream_chunk takes 16 more registers, and one scalar plane never needs more)
     TRY_(ProgAgeEuler, HNB_STREAM_WAVES)
     TRY_(ProgAccel, HNB_STREAM_WAVES)
     TRY_(ProgDrag, HNB_STREAM_WAVES)
@@ -239,6 +248,9 @@ struct HnbContext {
     uint32_t set_frames = 0;        // statistics: frames with a launch served by the set kernels
     uint32_t set_failed_builds = 0; // statistics: background compilations of a set module that failed (each population is tried once)
     std::string set_log;            // why the last build failed
+    // hnb_simulate_steps
+    bool fuse_steps = true;         // HNB_OPT_FUSE_STEPS: provable spans of list-free frames run as one launch per program
+    HnbStepStats step_stats{};      // hnb_ctx_step_stats
 };
 
 struct HnbProgram {
@@ -255,6 +267,15 @@ struct HnbProgram {
     uint32_t age_cohort_mode = HNB_AGE_COHORT_AUTO;   // HNB_OPT_AGE_COHORT as it stood when the program was created (fixed in the program from then on)
     bool auto_materialise = false;  // HNB_AGE_COHORT_AUTO, the render modifiers read AGE and the effect is large: cohorts, and the update keeps the plane current (SlotArgs::age_current)
     StreamLaunchFn stream_launch = nullptr;  // specialised (or interpreted) streaming kernel for this update stream
+    StreamLaunchFn stream_launch_fused = nullptr;   // ... its instantiation for several frames in one launch (pre-built sequences only)
+    // hnb_simulate_steps: fuse_span >= 2 - the frame being enqueued is the first of a span of that many frames this program runs in ONE launch (proven by
+    // plan::prove_fused_span; fuse_ublocks = the span's parameter blocks, [instance][step][n_uregs]); fused_left - frames of the context still to come that
+    // an earlier launch of this program already covered: the program sits them out
+    uint32_t fuse_span = 1, fused_left = 0;
+    uint32_t safe_launches = 0;              // update launches of this program so far: the parity of the no-death bound rows (SlotArgs::safe_parity). Not frames_run: a fused launch of an even
+                                             // number of frames would write the row its own publisher is re-arming
+    std::vector<uint32_t> fuse_ublocks;
+    uint32_t fused_frames = 0;               // statistics
     const char* stream_kernel_name = "";
     // kernels specialised for this program at creation (hnb_jit.h); null = the ahead-of-time kernels run
     hipModule_t jit_module = nullptr;
@@ -339,6 +360,10 @@ struct HnbEffect {
     uint32_t seed = 0;
     float xf[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
     std::vector<uint32_t> props;
+    // inputs of the steps of the next hnb_simulate_steps (hnb_effect_set_frames_ahead): [ahead_n] spawn counts and seeds, [ahead_n][12] transforms or none
+    uint32_t ahead_n = 0;
+    std::vector<uint32_t> ahead_spawn, ahead_seed;
+    std::vector<float> ahead_xf;
 };
 
 static_assert(HNB_COMM_ID_BYTES == comm::kNcclUniqueIdBytes, "HNB_COMM_ID_BYTES is sizeof(ncclUniqueId)");
@@ -696,7 +721,7 @@ void free_tables(HnbProgram* p) {
 }
 
 size_t frame_bytes_for(const HnbProgram* p, uint32_t n) {
-    return (size_t)n * sizeof(DevFrameInst) + (size_t)n * p->dev.n_uregs * 4 + (size_t)n * 4 + 16;  // + packed init_block_start[]
+    return (size_t)n * sizeof(DevFrameInst) + (size_t)n * p->dev.n_uregs * 4 * p->fuse_span + (size_t)n * 4 + 16;  // + packed init_block_start[]; fuse_span parameter blocks per instance
 }
 
 // Grow the per-program device tables to hold `need` instances, preserving state.
@@ -1046,6 +1071,7 @@ int hnb_ctx_set_option(HnbContext* ctx, uint32_t option, uint32_t value) {
         case HNB_OPT_STREAM_HINTS: ctx->stream_hints = value != 0u; return HNB_OK;
         case HNB_OPT_DIRECT_UPLOAD: ctx->direct_upload = value != 0u; return HNB_OK;   // (ensure_stage re-creates the slots of the other kind before the next frame)
         case HNB_OPT_JIT_ASYNC: ctx->jit_async = value != 0u; return HNB_OK;
+        case HNB_OPT_FUSE_STEPS: ctx->fuse_steps = value != 0u; return HNB_OK;
         case HNB_OPT_SET_MODULE:
             if (value > HNB_SET_MODULE_BACKGROUND) return fail(HNB_ERR_INVALID_ARG, "unknown set-module mode %u", value);
             ctx->set_mode = value;
@@ -1106,7 +1132,7 @@ int hnb_program_create(HnbContext* ctx, const void* blob, size_t blob_size, HnbP
     }
     p->age_cohort_mode = ctx->popt.age_cohort;
     p->auto_materialise = ctx->popt.age_cohort == HNB_AGE_COHORT_AUTO && d.age_cohort != 0u && (h.render_reads_lo >> HNB_ATTR_AGE & 1u) != 0u;
-    if (p->update_streams) select_stream_kernel(reinterpret_cast<const Ins*>(b + h.update_off), h.update_len, &p->stream_launch, &p->stream_kernel_name);
+    if (p->update_streams) select_stream_kernel(reinterpret_cast<const Ins*>(b + h.update_off), h.update_len, &p->stream_launch, &p->stream_kernel_name, &p->stream_launch_fused);
     if (!p->wide_file && jit::enabled()) {
         p->h_init.assign(reinterpret_cast<const Ins*>(b + h.init_off), reinterpret_cast<const Ins*>(b + h.init_off) + h.init_len);
         p->h_update.assign(reinterpret_cast<const Ins*>(b + h.update_off), reinterpret_cast<const Ins*>(b + h.update_off) + h.update_len);
@@ -1526,6 +1552,34 @@ int hnb_program_set_frames(HnbProgram* prog, uint32_t first, uint32_t count, con
     return HNB_OK;
 }
 
+int hnb_effect_set_frames_ahead(HnbEffect* fx, uint32_t n_steps, const uint32_t* spawn_counts, const uint32_t* seeds, const float* transforms3x4) {
+    if (!fx || (n_steps && (!spawn_counts || !seeds))) return fail(HNB_ERR_INVALID_ARG, "NULL argument");
+    fx->ahead_n = n_steps;
+    fx->ahead_spawn.assign(spawn_counts, spawn_counts + n_steps);
+    fx->ahead_seed.assign(seeds, seeds + n_steps);
+    if (transforms3x4) fx->ahead_xf.assign(transforms3x4, transforms3x4 + (size_t)n_steps * 12);
+    else fx->ahead_xf.clear();
+    return HNB_OK;
+}
+
+int hnb_program_set_frames_ahead(HnbProgram* prog, uint32_t first, uint32_t count, uint32_t n_steps, const uint32_t* spawn_counts, const uint32_t* seeds,
+                                 const float* transforms3x4) {
+    if (!prog || ((uint64_t)count * n_steps && (!spawn_counts || !seeds))) return fail(HNB_ERR_INVALID_ARG, "NULL argument");
+    if ((size_t)first + count > prog->effects.size()) return fail(HNB_ERR_INVALID_ARG, "instance range [%u, %u) exceeds the %zu instances of the program", first, first + count, prog->effects.size());
+    for (uint32_t i = 0; i < count; ++i) {   // step-major arrays: [n_steps][count]
+        HnbEffect* fx = prog->effects[first + i];
+        fx->ahead_n = n_steps;
+        fx->ahead_spawn.resize(n_steps); fx->ahead_seed.resize(n_steps);
+        fx->ahead_xf.resize(transforms3x4 ? (size_t)n_steps * 12 : 0u);
+        for (uint32_t s = 0; s < n_steps; ++s) {
+            fx->ahead_spawn[s] = spawn_counts[(size_t)s * count + i];
+            fx->ahead_seed[s] = seeds[(size_t)s * count + i];
+            if (transforms3x4) memcpy(&fx->ahead_xf[(size_t)s * 12], transforms3x4 + ((size_t)s * count + i) * 12, 12 * sizeof(float));
+        }
+    }
+    return HNB_OK;
+}
+
 int hnb_effect_index(HnbEffect* fx, uint32_t* out_index) {
     if (!fx || !out_index) return fail(HNB_ERR_INVALID_ARG, "NULL argument");
     *out_index = fx->index;
@@ -1576,7 +1630,7 @@ static SlotArgs slot_args_of(const HnbContext* ctx, const HnbProgram* p, uint32_
     sa.age_current = p->auto_materialise ? 1u : 0u;   // HNB_AGE_COHORT_AUTO: the render modifiers read AGE after every frame
     sa.frame_phase = p->frames_run & 15u;
     sa.horizon_off = p->dev.horizon_off; sa.horizon = p->horizon_eligible ? 1u : 0u;
-    if (p->skip_facts.eligible) { sa.safe_words = p->d_safe; sa.safe_host = p->h_safe; sa.safe_parity = p->frames_run & 1u; sa.publish_tag = p->frames_run - 1u; sa.safe_stride = p->table_cap * p->dev.chunks_per_inst; }
+    if (p->skip_facts.eligible) { sa.safe_words = p->d_safe; sa.safe_host = p->h_safe; sa.safe_parity = p->safe_launches & 1u; sa.publish_tag = p->frames_run - 1u; sa.safe_stride = p->table_cap * p->dev.chunks_per_inst; }
     sa.skip_lists = p->plan.skip_lists ? 1u : 0u;
     sa.meta_in = p->d_meta[par]; sa.meta_out = p->d_meta[par ^ 1];
     sa.fault = p->d_fault;
@@ -1722,6 +1776,7 @@ static void stage_program_frame(HnbContext* ctx, HnbProgram* p, uint32_t slot, s
     const float sim[6] = {ctx->sim.time, ctx->sim.delta_time, ctx->sim.virtual_time, ctx->sim.virtual_delta_time,
                           ctx->sim.real_time, ctx->sim.real_delta_time};
     const uint32_t nu = p->dev.n_uregs;
+    const uint32_t span = p->fuse_span;   // >= 2: the first frame of a fused span (plan_fused_spans): `span` parameter blocks per instance, already evaluated
     uint32_t blocks = 0;
     uint64_t cpu_spawns = 0;
     for (uint32_t i = 0; i < n; ++i) if (p->effects[i]->simulated && !p->effects[i]->parent) cpu_spawns += p->effects[i]->spawn_count;
@@ -1757,12 +1812,13 @@ static void stage_program_frame(HnbContext* ctx, HnbProgram* p, uint32_t slot, s
         plan::InstanceFrame& inf = inst_frames[i];
         inf.simulated = fx->simulated; inf.has_parent = fx->parent != nullptr; inf.spawn_count = fx->spawn_count;
         inf.event_capacity = fx->parent ? fx->parent->channels[fx->parent_channel].capacity : 0u;
-        inf.ublock = ublocks + (size_t)i * nu;
+        inf.ublock = ublocks + (size_t)i * nu * span;
         memcpy(fi[i].xf, fx->xf, sizeof fx->xf);
         // Parameter block: the uniform stream (literals, properties, sim params and every
         // expression built only from them) evaluated here, once per instance per frame.
         // (instances with the same property values share the result: thousands of instances of one effect cost one evaluation)
-        if (nu) {
+        if (nu && span >= 2u) memcpy(ublocks + (size_t)i * nu * span, p->fuse_ublocks.data() + (size_t)i * nu * span, (size_t)nu * span * 4);
+        else if (nu) {
             if (i > 0 && fx->props == p->effects[i - 1]->props) memcpy(ublocks + (size_t)i * nu, ublocks + (size_t)(i - 1) * nu, (size_t)nu * 4);
             else uniform_run(p->uniform_code.data(), (uint32_t)p->uniform_code.size(), fx->props.data(), sim, ublocks + (size_t)i * nu, nu);
         }
@@ -1770,7 +1826,8 @@ static void stage_program_frame(HnbContext* ctx, HnbProgram* p, uint32_t slot, s
     // ---- the frame's proofs (hnb_plan.h): pure functions of the facts fixed at program creation, the history they carry and these inputs
     plan::FramePlan& pl = p->plan;
     pl = plan::FramePlan();
-    {
+    if (span >= 2u) pl.skip_lists = true;   // proven for every frame of the span, the history advanced over all of them (plan::prove_fused_span)
+    else {
         const unsigned long long pub = *reinterpret_cast<volatile unsigned long long*>(p->h_safe);   // {frame, bound} the device published: no read-back
         pl.skip_lists = plan::prove_skip_lists(p->skip_facts, p->skip_hist, p->frames_run, inst_frames.data(), n, plan::SkipPublished{(uint32_t)pub, (uint32_t)(pub >> 32)}, ctx->skip_lists);
     }
@@ -1790,7 +1847,8 @@ static void stage_program_frame(HnbContext* ctx, HnbProgram* p, uint32_t slot, s
     pl.lists = !(p->update_streams && pl.skip_lists);  // false: proven no spawn, no casualty; the update kernel rotates the counters
     if (p->skip_facts.eligible && !p->tick_sign_seen)
         for (uint32_t i = 0; i < n; ++i)
-            if (inst_frames[i].simulated && !plan::nonneg_not_nan(plan::uword(inst_frames[i], p->skip_facts.dt_operand)) ) p->tick_sign_seen = true;
+            for (uint32_t s = 0; s < span; ++s)   // (every frame of a fused span)
+                if (inst_frames[i].simulated && !plan::nonneg_not_nan(inst_frames[i].ublock[(size_t)s * nu + (p->skip_facts.dt_operand & 0xffu)])) p->tick_sign_seen = true;
     if (pl.ribbon.ring && !pl.lists) pl.ribbon.ring = false;   // (nothing spawns, nothing can die: the list stands, head and all)
     p->dev.ring = pl.ribbon.ring ? 1u : 0u;
     pl.slot_init = plan::plan_slot_init(p->slot_init_eligible, ctx->slot_init, p->dev.capacity, p->dev.chunks_per_inst, inst_frames.data(), n);
@@ -1811,7 +1869,7 @@ static void stage_program_frame(HnbContext* ctx, HnbProgram* p, uint32_t slot, s
     }
     pl.independent = p->hdr.n_event_channels == 0 && !(p->hdr.flags & HNB_PROG_READS_PARENT) && n != 0u;
     for (uint32_t i = 0; i < n; ++i) if (p->effects[i]->parent) pl.independent = false;
-    uint32_t* init_start = ublocks + (size_t)n * nu;  // packed copy of init_block_start for k_init's search
+    uint32_t* init_start = ublocks + (size_t)n * nu * span;  // packed copy of init_block_start for k_init's search
     for (uint32_t i = 0; i < n; ++i) init_start[i] = fi[i].init_block_start;
     stage_off += (frame_bytes_for(p, n) + 255u) & ~(size_t)255u;
     pl.init_blocks = blocks;
@@ -2177,7 +2235,14 @@ static int enqueue_program_update(HnbContext* ctx, HnbProgram* p, hipStream_t st
         // (served by k_update_jobs / k_update_generic_wide_jobs: enqueue_update_passes)
     } else if (p->update_streams) {
         SlotArgs sa = slot_args_of(ctx, p, n, write_died);
-        if (p->jit_update) {
+        ctx->step_stats.update_launches += 1;
+        if (p->fuse_span >= 2u) {   // frames F .. F + span - 1 of this program in one launch (hnb_simulate_steps)
+            sa.fuse_steps = p->fuse_span;
+            p->stream_launch_fused(total_chunks, st, sa, p->d_inst_base, dfi, dub, cb);
+            ctx->step_stats.fused_launches += 1;
+            ctx->step_stats.fused_frames += p->fuse_span;
+            p->fused_frames += p->fuse_span;
+        } else if (p->jit_update) {
             void* ka[] = {&sa, &p->d_inst_base, &dfi, &dub, &cb};
             HIP_TRY(hipModuleLaunchKernel(p->jit_update, total_chunks, 1, 1, kBlock, 1, 1, 0, st, ka, nullptr));
         } else {
@@ -2187,6 +2252,7 @@ static int enqueue_program_update(HnbContext* ctx, HnbProgram* p, hipStream_t st
         // a generic program of a few chunks: one workgroup per 256 slots (k_update_slots_generic's `split`), while the grid still fits the GPU at once
         uint32_t split = total_chunks <= kGenericSplitMaxChunks ? 1u : 0u;
         const uint32_t grid = split ? total_chunks * (kChunk / kBlock) : total_chunks;
+        ctx->step_stats.update_launches += 1;
         if (p->jit_update) {
             uint32_t dm = write_died;
             void* ka[] = {&p->dev, &p->d_inst_base, &dfi, &dub, &cb, &dm, &split};
@@ -2197,7 +2263,7 @@ static int enqueue_program_update(HnbContext* ctx, HnbProgram* p, hipStream_t st
     if (timed) { hipEventRecord(tu.b, st); ctx->t_update.push_back(tu); }
     const CompactArgs ca = compact_args_of(p);
     const bool lists = p->plan.lists;
-    if (!lists) p->skipped_frames += 1;
+    if (!lists) p->skipped_frames += p->fuse_span;
     else if (ca.suffix_dead) p->suffix_frames += 1;
     if (lists && p->dev.n_event_channels) {  // order this frame's spawn events (by list row) into the children's buffers
         k_emit_count<<<total_chunks, kBlock, 0, st>>>(p->dev, p->d_inst_base, p->d_meta[par], dfi, cb);
@@ -2210,6 +2276,7 @@ static int enqueue_program_update(HnbContext* ctx, HnbProgram* p, hipStream_t st
     }
     // lists: only the instances that lost particles have anything to do
     if (!p->plan.lists_merged) {  // (merged: the lists, and the ribbon sort behind them, follow after the last program's update)
+        if (lists) ctx->step_stats.list_launches += ((!p->slot_order && !ca.suffix_dead) ? 2u : 1u) + (p->slot_order ? 2u : 0u);
         if (lists && !p->slot_order && !ca.suffix_dead) k_count_rows<<<total_chunks, kBlock, 0, st>>>(ca, p->d_inst_base, p->d_meta[par], dfi, cb);
         if (lists) k_compact<<<total_chunks, kBlock, 0, st>>>(ca, p->d_inst_base, p->d_meta[par], p->d_meta[par ^ 1], dfi, cb);
         if (lists && p->slot_order) {  // rebuild the lists in increasing slot order (instances without a casualty or spawn return at once)
@@ -2235,6 +2302,9 @@ static int enqueue_update_passes(HnbContext* ctx, const std::vector<HnbProgram*>
         }
     }
     // (the merged updates first: every init pass is enqueued, and a merged program's own list kernels may follow in the loop below)
+    if (fj.stream[0].wgs + fj.stream[1].wgs + fj.generic[0].wgs) ctx->step_stats.update_launches += 1;
+    if (fj.generic[1].wgs) ctx->step_stats.update_launches += 1;
+    if (fj.n_lists) ctx->step_stats.list_launches += 2;
     if (fj.update_set) {
         const void *sj0 = fj.stream[0].d_jobs, *sj1 = fj.stream[1].d_jobs, *pj = fj.generic[0].d_jobs;
         uint32_t n0 = fj.stream[0].n, n1 = fj.stream[1].n, np = fj.generic[0].n, b0 = fj.stream[0].wgs, b1 = fj.stream[0].wgs + fj.stream[1].wgs;
@@ -2269,13 +2339,13 @@ static int enqueue_update_passes(HnbContext* ctx, const std::vector<HnbProgram*>
 // One simulated frame, in the reference's order (src/render/mod.rs:6975-7370): every effect's init
 // pass, parents before children, THEN every effect's update pass. Spawn events appended by a parent's
 // update in frame N are consumed by its children's init in frame N+1.
-int hnb_simulate(HnbContext* ctx) {
-    if (!ctx) return fail(HNB_ERR_INVALID_ARG, "ctx is NULL");
+// (hnb_simulate_steps: a program whose earlier fused launch already covers this frame - HnbProgram::fused_left - takes no part in it)
+static int simulate_frame(HnbContext* ctx) {
     HIP_TRY(hipSetDevice(ctx->device));
     install_finished_jit(ctx);
-    std::vector<HnbProgram*> order;
+    std::vector<HnbProgram*> order, covered;
     for (HnbProgram* p : ctx->programs)
-        if (!p->effects.empty()) order.push_back(p);
+        if (!p->effects.empty()) (p->fused_left ? covered : order).push_back(p);
     std::stable_sort(order.begin(), order.end(), [](const HnbProgram* x, const HnbProgram* y) { return x->level < y->level; });
     const bool timed = ctx->timing && (ctx->timing_tick % ctx->timing) == 0;
     // validate every instance before any per-frame state is touched: a failed call must leave the frame's inputs intact
@@ -2319,19 +2389,140 @@ int hnb_simulate(HnbContext* ctx) {
         if (ctx->side_stream && (fj.forked || fj.heavy)) hipStreamSynchronize(ctx->side_stream);
         return rc;
     }
+    for (HnbProgram* p : covered) p->fused_left -= 1;
     for (HnbProgram* p : order) {
-        p->ring += 1;
-        p->parity ^= 1u;
-        p->frames_run += 1;
+        // (a fused span: the host-side clocks of the program go where `fuse_span` single frames would leave them - the alternating walk and the cohort
+        // re-check follow frames_run, the metadata rows and the casualty counters the parity; the context's frames that follow find the program covered)
+        const uint32_t span = p->fuse_span;
+        p->fused_left = span - 1u;
+        p->fuse_span = 1u;
+        p->safe_launches += 1;
+        p->ring += span;
+        p->parity ^= span & 1u;
+        p->frames_run += span;
         if (p->horizon_eligible && p->plan.lists) p->hz_parity ^= 1u;   // k_count_rows / k_compact moved the horizons to the other half
         if (p->plan.ribbon.ring) { p->ring_live = true; p->ring_frames += 1; }
         else if (p->plan.lists) p->ring_live = false;                   // (k_compact ran with force_rewrite: every instance's list is linear again)
     }
     if (!order.empty()) HIP_TRY(hipEventRecord(ctx->stage_done[slot], ctx->stream));
-    for (HnbProgram* p : order)
+    for (HnbProgram* p : ctx->programs)
         for (HnbEffect* fx : p->effects) fx->spawn_count = 0;  // a spawn request is consumed by exactly one (enqueued) frame
     ctx->frame += 1;
+    ctx->step_stats.frames += 1;
     if (ctx->timing) ctx->timing_tick += 1;
+    return HNB_OK;
+}
+
+static void drop_ahead_inputs(HnbContext* ctx) {
+    for (HnbProgram* p : ctx->programs)
+        for (HnbEffect* fx : p->effects) { fx->ahead_n = 0; fx->ahead_spawn.clear(); fx->ahead_seed.clear(); fx->ahead_xf.clear(); }
+}
+
+int hnb_simulate(HnbContext* ctx) {
+    if (!ctx) return fail(HNB_ERR_INVALID_ARG, "ctx is NULL");
+    const int rc = simulate_frame(ctx);
+    drop_ahead_inputs(ctx);   // (inputs given ahead belong to the next hnb_simulate_steps: a single frame in between makes them stale)
+    return rc;
+}
+
+// ---- several frames per call ---------------------------------------------------------------------------------------------------------------
+// hnb_simulate_steps = for every step: the step's clocks and per-effect inputs, then one frame as above - except that a program for which the host can
+// prove, NOW, that the next S >= 2 steps are list-free (plan::prove_fused_span: prove_skip_lists step by step against the bound the device has
+// published) runs them in ONE launch of its fused streaming kernel in the first of those frames and sits the other S - 1 out. Such a program is
+// independent of every other (SkipFacts::eligible: no spawn events in or out, no parent), so running ahead of the rest of the context inside one call
+// is not observable: everything that reads state is ordered behind the whole call.
+constexpr uint32_t kFuseBlockWords = 16384;   // a fused span's parameter blocks: at most 64 KiB of the frame's staging slot per program
+static bool fuse_candidate(const HnbContext* ctx, const HnbProgram* p) {
+    const uint64_t chunks = (uint64_t)p->effects.size() * p->dev.chunks_per_inst;
+    return ctx->fuse_steps && ctx->skip_lists && !ctx->break_proof && ctx->timing == 0u &&      // (kernel timing: one launch per frame stays attributable; the test hook claims without proof)
+           p->fused_left == 0u && p->update_streams && p->skip_facts.eligible && !p->has_ribbons && p->hdr.n_event_channels == 0u &&
+           p->stream_launch_fused && !p->jit_update && !p->jit_pending &&                       // a pre-built op sequence (the kernels specialised at run time have no fused form)
+           chunks > kSceneMaxChunks;                                                            // never a candidate for the merged launches / set modules: its own launch
+}
+// params / first_step: the steps still to run, and the index of the first of them inside the call (the effects' ahead inputs are indexed by it)
+static void plan_fused_spans(HnbContext* ctx, const HnbSimParams* params, uint32_t remaining, uint32_t first_step) {
+    std::vector<plan::InstanceFrame> rows;
+    std::vector<uint32_t> blocks;
+    for (HnbProgram* p : ctx->programs) {
+        p->fuse_span = 1u;
+        if (p->effects.empty() || !fuse_candidate(ctx, p)) continue;
+        const uint32_t n = (uint32_t)p->effects.size(), nu = p->dev.n_uregs;
+        plan::FuseLimits lim;
+        lim.max_steps = HNB_MAX_FUSED_STEPS; lim.block_words = kFuseBlockWords;
+        uint32_t most = std::min(remaining, plan::fused_span_cap(n, nu, lim));
+        auto spawn_of = [&](const HnbEffect* fx, uint32_t t) { return first_step + t < fx->ahead_n ? fx->ahead_spawn[first_step + t] : (t == 0u ? fx->spawn_count : 0u); };
+        for (uint32_t t = 0; t < most; ++t)   // (a step that spawns ends the span: its blocks need not be evaluated)
+            for (uint32_t i = 0; i < n; ++i)
+                if (p->effects[i]->simulated && spawn_of(p->effects[i], t) != 0u) most = t;
+        if (most < 2u) continue;
+        rows.assign((size_t)most * n, plan::InstanceFrame());
+        blocks.assign((size_t)most * n * nu + 1u, 0u);   // [step][instance][n_uregs]
+        for (uint32_t t = 0; t < most; ++t) {
+            const HnbSimParams& sp = params[t];
+            const float sim[6] = {sp.time, sp.delta_time, sp.virtual_time, sp.virtual_delta_time, sp.real_time, sp.real_delta_time};
+            for (uint32_t i = 0; i < n; ++i) {
+                const HnbEffect* fx = p->effects[i];
+                uint32_t* ub = blocks.data() + ((size_t)t * n + i) * nu;
+                if (nu) {
+                    if (i > 0 && fx->props == p->effects[i - 1]->props) memcpy(ub, ub - nu, (size_t)nu * 4);
+                    else uniform_run(p->uniform_code.data(), (uint32_t)p->uniform_code.size(), fx->props.data(), sim, ub, nu);
+                }
+                plan::InstanceFrame& inf = rows[(size_t)t * n + i];
+                inf.simulated = fx->simulated; inf.has_parent = fx->parent != nullptr; inf.spawn_count = spawn_of(fx, t);
+                inf.ublock = ub;
+            }
+        }
+        const unsigned long long pub = *reinterpret_cast<volatile unsigned long long*>(p->h_safe);
+        const uint32_t span = plan::prove_fused_span(p->skip_facts, p->skip_hist, p->frames_run, rows.data(), n, most, nu,
+                                                     plan::SkipPublished{(uint32_t)pub, (uint32_t)(pub >> 32)}, ctx->skip_lists, ctx->fuse_steps, true, lim);
+        if (span < 2u) continue;
+        p->fuse_span = span;
+        p->fuse_ublocks.resize((size_t)n * span * nu);   // [instance][step][n_uregs]: what the kernel indexes
+        for (uint32_t i = 0; i < n; ++i)
+            for (uint32_t t = 0; t < span; ++t)
+                if (nu) memcpy(p->fuse_ublocks.data() + ((size_t)i * span + t) * nu, blocks.data() + ((size_t)t * n + i) * nu, (size_t)nu * 4);
+    }
+}
+
+int hnb_simulate_steps(HnbContext* ctx, uint32_t n_steps, const HnbSimParams* params) {
+    if (!ctx) return fail(HNB_ERR_INVALID_ARG, "ctx is NULL");
+    if (n_steps == 0u) return HNB_OK;
+    if (!params) return fail(HNB_ERR_INVALID_ARG, "params is NULL");
+    // (what simulate_frame refuses before it touches anything, refused here before a span is planned: planning advances the proof's history)
+    for (HnbProgram* p : ctx->programs)
+        if (!p->parent_attrs.empty())
+            for (size_t i = 0; i < p->effects.size(); ++i)
+                if (!p->effects[i]->parent)
+                    return fail(HNB_ERR_INVALID_ARG, "effect #%zu reads its parent particle (InheritAttributeModifier / parent_attr) but has no parent: call hnb_effect_set_parent", i);
+    int rc = HNB_OK;
+    for (uint32_t s = 0; s < n_steps && rc == HNB_OK; ++s) {
+        ctx->sim = params[s];
+        for (HnbProgram* p : ctx->programs)
+            for (HnbEffect* fx : p->effects) {
+                if (s >= fx->ahead_n) continue;   // no inputs for this step: as a frame without hnb_effect_set_frame
+                fx->spawn_count = fx->ahead_spawn[s];
+                fx->seed = fx->ahead_seed[s];
+                if (!fx->ahead_xf.empty()) memcpy(fx->xf, &fx->ahead_xf[(size_t)s * 12], sizeof fx->xf);
+            }
+        if (n_steps - s >= 2u) plan_fused_spans(ctx, params + s, n_steps - s, s);
+        rc = simulate_frame(ctx);
+    }
+    for (HnbProgram* p : ctx->programs) {
+        if (rc != HNB_OK) {
+            // a frame of the call failed: the steps behind it were not enqueued. A span planned for the failed frame was not launched although the history
+            // already covers it - no older bound is trusted again -, and a program whose launch ran ahead must not sit out frames of a LATER call
+            if (p->fuse_span >= 2u) p->skip_hist.dirty = true;
+            p->fused_left = 0u;
+        }
+        p->fuse_span = 1u;
+    }
+    drop_ahead_inputs(ctx);
+    return rc;
+}
+
+int hnb_ctx_step_stats(HnbContext* ctx, HnbStepStats* out) {
+    if (!ctx || !out) return fail(HNB_ERR_INVALID_ARG, "NULL argument");
+    *out = ctx->step_stats;
     return HNB_OK;
 }
 
@@ -2696,7 +2887,8 @@ int hnb_jit_precompile(const void* blob, size_t blob_size) {
     if (streams) {
         StreamLaunchFn fn = nullptr;
         const char* name = "";
-        select_stream_kernel(reinterpret_cast<const Ins*>(b + h.update_off), h.update_len, &fn, &name);
+        StreamLaunchFn fused = nullptr;
+        select_stream_kernel(reinterpret_cast<const Ins*>(b + h.update_off), h.update_len, &fn, &name, &fused);
         aot_static = strcmp(name, "ProgInterp") != 0;
     }
     const jit::Request rq = make_jit_request(b, h, attrs.data(), streams, aot_static, ProgramOptions());   // (the default options: what a context starts with)

@@ -1297,7 +1297,7 @@ struct SlotArgs {
     uint32_t frame_phase;    // frames this program ran, mod 16: staggers the re-check of chunks known to hold mixed ages (cohort state 4)
     const Ins* update_code;
     // "No particle can die before ..." (below): safe_words = u32[2][safe_stride] float bits, the frame's minimum remaining life
-    // per chunk, double-buffered by safe_parity; safe_host = host-mapped {frame tag, bound bits} the host reads without any
+    // per chunk, double-buffered by safe_parity (the parity of the program's update LAUNCHES: a launch reads and re-arms row safe_parity ^ 1 and writes row safe_parity); safe_host = host-mapped {frame tag, bound bits} the host reads without any
     // synchronisation; publish_tag = index of the previous frame of this program. Null pointers: the program is not eligible.
     uint32_t* safe_words;
     unsigned long long* safe_host;
@@ -1318,6 +1318,9 @@ struct SlotArgs {
     uint32_t age_current;    // 1 (with age_cohort; HNB_AGE_COHORT_AUTO for an asset whose render modifiers read AGE): a chunk that keeps its common age in the
                              // value word ALSO writes it to the plane for its alive slots - write-only, 4 of the 8 bytes the cohort saves - so the AGE plane
                              // is current after every frame without a second pass over it (until round 6: a k_materialise_age launch behind every update)
+    uint32_t fuse_steps;     // S >= 2 (the FUSED instantiations only; hnb_simulate_steps): this launch is the frames F .. F+S-1 of the program, proven list-free
+                             // by the host one after the other (plan::prove_fused_span). `ublocks` then holds S parameter blocks per instance, step-major
+                             // inside the instance ([n_inst][S][n_uregs]); frame_phase and publish_tag describe frame F
 };
 
 // The deaths of a frame are known on the device only after its update ran, and HIP has no indirect dispatch: the list
@@ -1385,7 +1388,12 @@ __device__ __forceinline__ StreamLds& stream_lds() {
 
 // PROBE (tools/stream_probe.hip only; 0 in the product): 4 = skip stores, 8 = skip the program.
 // COHORT: compile the age-cohort paths in (programs that are eligible: SlotArgs::age_cohort); false leaves the kernel as it was.
-template <class PROG, int PROBE, bool COHORT>
+// FUSED (hnb_simulate_steps): S = SlotArgs::fuse_steps list-free frames of the program in this one launch. The planes are loaded once, the program runs
+// S times on the registers with step s's parameter block (the same IEEE operations in the same order as S launches), the planes are stored once; what
+// a frame decides from the AGE (flat path, lifetime culling, cohort check, no-death bound) is decided from the age after step S - the ticks are >= 0
+// by the host's proof, f32 addition is monotonic, so every intermediate age is below whatever the last one is below. A particle that fails is_alive in
+// ANY sub-step is a casualty of the launch and raises the fault flag, as a death in a list-free frame does. `false` leaves the single-frame code as it was.
+template <class PROG, int PROBE, bool COHORT, bool FUSED = false>
 __device__ __forceinline__ void update_stream_chunk(const SlotArgs& args, const uint64_t* __restrict__ inst_base, const DevFrameInst* __restrict__ fi,
                                                     const uint32_t* __restrict__ ublocks, const CompactBufs& cb,
                                                     const uint32_t wg, const uint32_t wg_total) {   // workgroup wg of the program's wg_total (k_update_slots_stream, k_update_stream_jobs)
@@ -1398,7 +1406,8 @@ __device__ __forceinline__ void update_stream_chunk(const SlotArgs& args, const 
     uint32_t (&s_amax)[kBlock / 64] = lds.amax;
     u4v (&s_xp)[2][kBlock / 64][kStepRows * 3u / 4u] = lds.xp;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const bool split = !COHORT && args.quarters == 4u;   // (SlotArgs::quarters; wave-uniform)
+    const bool split = !FUSED && !COHORT && args.quarters == 4u;   // (SlotArgs::quarters; wave-uniform)
+    const uint32_t S = FUSED ? args.fuse_steps : 1u;     // frames of this launch (wave-uniform)
     const uint32_t chunk = split ? chunk_of_workgroup(cb.xcd_remap, wg >> 2, wg_total >> 2) : chunk_of_workgroup(cb.xcd_remap, wg, wg_total);
     const uint32_t quarter = split ? (wg & 3u) : 0u;
     const uint32_t k = chunk / args.chunks_per_inst, j = chunk - k * args.chunks_per_inst;
@@ -1434,17 +1443,36 @@ __device__ __forceinline__ void update_stream_chunk(const SlotArgs& args, const 
     }
     if (args.skip_lists && j == 0u && quarter == 0u && tid == 0u) {  // counter rotation of a frame without spawn and casualty (k_compact's zero-casualty path)
         DevMeta o = args.meta_in[k];
+        if constexpr (FUSED) {
+            // S rotations: frame i of the span writes the row of parity (cb.parity ^ i): the last one and the one before it are the two rows that stand
+            // afterwards. Every rotation after the first only flips ref_write_index.
+            DevMeta before = o;
+            if (!frozen) {
+                o.max_update = o.alive_count; o.dead_count = 0u; o.spawned = 0u; o.instance_count = o.alive_count;
+                before = o;
+                o.ref_write_index ^= S & 1u;
+                before.ref_write_index ^= (S - 1u) & 1u;
+            }
+            DevMeta* row_in = const_cast<DevMeta*>(args.meta_in);
+            ((S & 1u) ? args.meta_out : row_in)[k] = o;
+            ((S & 1u) ? row_in : args.meta_out)[k] = before;
+            // (the word of cb.parity is zero on entry - the frame before re-armed it - and only a casualty of this launch, i.e. a wrong proof, adds to it:
+            // left alone, so that the count of a faulting launch survives as it does in a single frame)
+            cb.deaths[(size_t)(cb.parity ^ 1u) * cb.table_cap + k] = 0u;
+        } else {
         if (!frozen) {
             o.ref_write_index ^= 1u;
             o.max_update = o.alive_count; o.dead_count = 0u; o.spawned = 0u; o.instance_count = o.alive_count;
         }
         args.meta_out[k] = o;
         cb.deaths[(size_t)(cb.parity ^ 1u) * cb.table_cap + k] = 0u;
+        }
     }
     if (frozen) return;  // frozen instance
     char* base = global_ptr<char>(slab);
     VmUniforms U;
-    U.u = ublocks + (size_t)k * args.n_uregs;
+    U.u = ublocks + (size_t)k * args.n_uregs * S;   // (FUSED: the block of the span's first step; step s follows s * n_uregs words behind it)
+    auto uniforms_of = [&](const uint32_t s) { VmUniforms Us = U; Us.u = U.u + (size_t)s * args.n_uregs; return Us; };
     U.xf = fi[k].xf;
     float rem_min = __builtin_inff();  // min over this lane's particles that stay alive of (lifetime - age) - 1e-5 * lifetime
     char* p_pos = base + args.plane_off[0];
@@ -1466,7 +1494,11 @@ __device__ __forceinline__ void update_stream_chunk(const SlotArgs& args, const 
     // in a spawn / die steady state it never becomes uniform, and the bookkeeping of the check is a third of the per-particle path's
     // instructions - but in one frame of sixteen, staggered over the chunks; everywhere else state 4 is state 0: the plane holds the ages)
     const uint32_t ast_raw = COHORT ? astate[j] : 0u;  // wave-uniform
-    const bool mixed = COHORT && ast_raw == 4u && ((args.frame_phase + j) & 15u) != 0u;
+    bool check_due = ((args.frame_phase + j) & 15u) == 0u;
+    if constexpr (FUSED) {   // (a re-check that falls on any frame of the span is made once, on the ages the span ends with)
+        for (uint32_t s = 1; s < S; ++s) check_due = check_due || ((args.frame_phase + s + j) & 15u) == 0u;
+    }
+    const bool mixed = COHORT && ast_raw == 4u && !check_due;
     const uint32_t ast = ast_raw == 4u ? 0u : ast_raw;
     const float A = COHORT ? u2f(aval[j]) : 0.0f;
     uint32_t amin = 0xffffffffu, amax = 0u;               // bit patterns of the ages of the particles that stay alive
@@ -1475,8 +1507,20 @@ __device__ __forceinline__ void update_stream_chunk(const SlotArgs& args, const 
     float* lmin = reinterpret_cast<float*>(base + args.lmin_off);
     const float Lm = cull ? lmin[j] : 0.0f;           // 0 (or anything not > 0): unknown, every step loads the lifetimes
     const float dt_tick = cull ? uf(U, args.dt_operand) : 0.0f;
+    // the age after this launch's frames: mac_age_tick's arithmetic, one addition per frame in frame order
+    auto age_after = [&](float a) {
+        if constexpr (FUSED) {
+            for (uint32_t s = 0; s < S; ++s) a = a + uf(uniforms_of(s), args.dt_operand);
+            return a;
+        } else return a + dt_tick;
+    };
     if (args.horizon && j == 0u && quarter == 0u && tid == 0u) {       // the instance's clock: once per simulated frame (frozen instances returned above)
         double* clk = horizon_view(base, args.horizon_off, args.chunks_per_inst).clock;
+        if constexpr (FUSED) {   // the same S double additions in the same order
+            double c = *clk;
+            for (uint32_t s = 0; s < S; ++s) { const float t = cull ? uf(uniforms_of(s), args.dt_operand) : 0.0f; c = c + (double)(t > 0.0f ? t : 0.0f) * (1.0 + 0x1p-16); }
+            *clk = c;
+        } else
         *clk = *clk + (double)(dt_tick > 0.0f ? dt_tick : 0.0f) * (1.0 + 0x1p-16);
     }
     float wave_min = __builtin_inff();                // minimum lifetime of the particles that stay alive (steps that loaded them)
@@ -1490,11 +1534,11 @@ __device__ __forceinline__ void update_stream_chunk(const SlotArgs& args, const 
     // (tools/flat_probe.hip, 16.7M particles, alternating walk): 0.138-0.142 ms with the quads, 0.119-0.122 ms flat.
     bool flat = false;
     if constexpr (PROG::kFlat && COHORT && PROBE == 0) {
-        flat = chunk_full && ast == 1u && cull && Lm > 0.0f && (A + dt_tick < Lm) && (fl & 3u) == 3u && !(fl & 128u);
+        flat = chunk_full && ast == 1u && cull && Lm > 0.0f && (age_after(A) < Lm) && (fl & 3u) == 3u && !(fl & 128u);
     }
     if (flat) {
         if constexpr (PROG::kFlat && COHORT && PROBE == 0) {
-            const float A2 = A + dt_tick;   // mac_age_tick's arithmetic; A2 < Lm <= every lifetime: every particle of the chunk stays alive
+            const float A2 = age_after(A);   // mac_age_tick's arithmetic; A2 < Lm <= every lifetime: every particle of the chunk stays alive
             u4v* pw = reinterpret_cast<u4v*>(p_pos + (size_t)j * (kChunk * 12u)) + wave * (kWaveRows * 3u / 4u);
             u4v* vw = reinterpret_cast<u4v*>(p_vel + (size_t)j * (kChunk * 12u)) + wave * (kWaveRows * 3u / 4u);
             const uint32_t rot = lane % 3u;   // component of this lane's first float in every word it takes: (word index) mod 3 = (3 step + w + lane) mod 3, w added below
@@ -1514,6 +1558,9 @@ __device__ __forceinline__ void update_stream_chunk(const SlotArgs& args, const 
                     P[w][0] = u2f(a.x); P[w][1] = u2f(a.y); P[w][2] = u2f(a.z); P[w][3] = u2f(a.w);
                     V[w][0] = u2f(b.x); V[w][1] = u2f(b.y); V[w][2] = u2f(b.z); V[w][3] = u2f(b.w);
                 }
+                if constexpr (FUSED) {
+                    for (uint32_t s = 0; s < S; ++s) PROG::run_flat(args.update_code, P, V, rot, uniforms_of(s));
+                } else
                 PROG::run_flat(args.update_code, P, V, rot, U);
 #pragma unroll
                 for (uint32_t w = 0; w < 3; ++w) {
@@ -1587,7 +1634,7 @@ __device__ __forceinline__ void update_stream_chunk(const SlotArgs& args, const 
         if (cull && Lm > 0.0f && (COH || !mixed)) {
             bool may_die = false;
 #pragma unroll
-            for (int p = 0; p < 4; ++p) may_die = may_die || (was[p] && !(X.age[p] + dt_tick < Lm));
+            for (int p = 0; p < 4; ++p) may_die = may_die || (was[p] && !(age_after(X.age[p]) < Lm));
             need_life = __any(may_die);
         }
         if (any && (fl & 8u)) {
@@ -1603,6 +1650,16 @@ __device__ __forceinline__ void update_stream_chunk(const SlotArgs& args, const 
             }
         }
         if (!need_life) loaded_all = false;
+        if constexpr (FUSED) {
+            bool gone[4] = {false, false, false, false};   // failed is_alive in some sub-step: a casualty of the launch (the fault flag below)
+            for (uint32_t s = 0; s < S; ++s) {
+                PROG::template run<4>(args.update_code, args.update_len, X, uniforms_of(s));
+#pragma unroll
+                for (int p = 0; p < 4; ++p) gone[p] = gone[p] || !X.alive[p];
+            }
+#pragma unroll
+            for (int p = 0; p < 4; ++p) X.alive[p] = !gone[p];
+        } else
         if constexpr (!(PROBE & 8)) PROG::template run<4>(args.update_code, args.update_len, X, U);
         if constexpr (!(PROBE & 4)) {
             // (a plane that is stored without having been loaded has no staged copy: the direct path)
@@ -1753,6 +1810,8 @@ steps_done:
         if (args.safe_words) {  // one word per chunk and frame parity, plain store (same-address atomics from 8 XCDs cost ~0.1 us EACH)
             float r = fminf(fminf(s_rem[0], s_rem[1]), fminf(s_rem[2], s_rem[3]));
             r = r > 0.0f ? r : 0.0f;  // non-negative floats order like their bit patterns; +inf: no live particle in the chunk
+            // (row safe_parity whatever the launch covers: the publisher above reads and re-arms row safe_parity ^ 1 while the other workgroups of the launch
+            // already write here - the two rows must differ for every S, which is why the parity counts LAUNCHES, not frames)
             uint32_t* word = args.safe_words + (size_t)args.safe_parity * args.safe_stride + chunk;
             if (split) atomicMin(word, f2u(r));   // the chunk's four quarters (the word was +inf: the publisher of the frame before left it so)
             else *word = f2u(r);
@@ -1769,13 +1828,14 @@ steps_done:
     }
 }
 
-template <class PROG, int WAVES, int PROBE = 0, bool COHORT = false>
+// FUSED: SlotArgs::fuse_steps frames of the program in one launch (hnb_simulate_steps; update_stream_chunk's FUSED) - instantiations of their own, so
+// that the code generated for single frames does not change.
+template <class PROG, int WAVES, int PROBE = 0, bool COHORT = false, bool FUSED = false>
 __global__ void __launch_bounds__(kBlock, WAVES)
 k_update_slots_stream(const SlotArgs args, const uint64_t* __restrict__ inst_base, const DevFrameInst* __restrict__ fi,
                       const uint32_t* __restrict__ ublocks, const CompactBufs cb) {
-    update_stream_chunk<PROG, PROBE, COHORT>(args, inst_base, fi, ublocks, cb, blockIdx.x, gridDim.x);
+    update_stream_chunk<PROG, PROBE, COHORT, FUSED>(args, inst_base, fi, ublocks, cb, blockIdx.x, gridDim.x);
 }
-
 #ifndef HNB_JIT_TU
 // ---- k_update_slots_stream_age (r6): the update that is ONE AGE_TICK, as a kernel of its own ------------------------------------------------------------
 // ribbon.rs, lightning.rs: trails that do not move. `age += dt; alive = age < lifetime` over one scalar plane is 9 bytes per particle, and a 4M-particle

@@ -4,6 +4,7 @@
 // hanabi_amd.hip calls them once per program and frame and stores the result in an immutable FramePlan.
 //
 //   prove_skip_lists      "nothing spawns and nothing can die this frame": the update rotates the counters itself, no list kernels
+//   prove_fused_span      "... and so do the next S frames": hnb_simulate_steps runs them in one launch of the fused streaming kernel
 //   prove_ribbon_order    "the head of a ribbon effect's list is still sorted" / "this frame's spawns sort in front of everything" /
 //                         "the frame's casualties are the last rows of the list": partial sort, sort by rotation, no k_count_rows
 //   horizon_usable        "every tick of the frame is finite": k_count_rows may trust the row-chunk death horizons
@@ -75,6 +76,42 @@ inline bool prove_skip_lists(const SkipFacts& facts, SkipHistory& h, uint32_t fr
     if (pub.tag == 0xffffffffu || !(pub.tag < frame_no) || pub.tag < h.last_dirty || frame_no - pub.tag > kSkipMaxAge || !nonneg_not_nan(pub.bound_bits)) return false;
     const double ticks = h.cum_tick[frame_no & 127u] - h.cum_tick[pub.tag & 127u];   // frames tag + 1 .. F
     return ticks * (1.0 + 1e-6) < (double)as_float(pub.bound_bits);
+}
+
+// ---- several frames in one launch (hnb_simulate_steps) ------------------------------------------------------------------------------------
+// If the proof above holds for the frames F .. F+S-1 of a program, the S updates of a slot depend on nothing outside the slot: one launch of
+// the fused streaming kernel (hnb_kernels.hip.h, update_stream_chunk<.., FUSED>) loads the planes once, runs the program S times with step s's
+// parameter block and stores once. prove_fused_span returns S, the longest provable PREFIX of the `n_steps` steps the caller has inputs for:
+// it IS prove_skip_lists applied step by step to a copy of the history, against the one bound the host can see now (an older bound than a
+// single frame later in the span might have found: never a stronger statement), cut at
+//   lim.max_steps       HNB_MAX_FUSED_STEPS
+//   lim.block_words     what the program's share of the frame's parameter block holds: S x instances x n_uregs words
+//   program_eligible    what the caller knows beyond SkipFacts (its own launch of k_update_slots_stream, no ribbons, no timed frame, no test hook)
+// A span needs two steps: below that the return value is 0, the history is NOT touched and the frame takes the single-frame path (which calls
+// prove_skip_lists itself). Otherwise the history is left exactly where S calls of prove_skip_lists leave it.
+// inst: [n_steps][n] rows, step-major; every row's ublock is that step's evaluation of the uniform stream. Ticks may differ between steps.
+struct FuseLimits { uint32_t max_steps = 8, block_words = 16384; };
+inline uint32_t fused_span_cap(uint32_t n, uint32_t n_uregs, FuseLimits lim) {
+    const uint64_t per_step = (uint64_t)(n ? n : 1u) * (n_uregs ? n_uregs : 1u);
+    const uint64_t fit = lim.block_words / per_step;
+    return (uint32_t)(fit < lim.max_steps ? fit : lim.max_steps);
+}
+inline uint32_t prove_fused_span(const SkipFacts& facts, SkipHistory& h, uint32_t frame_no, const InstanceFrame* inst, uint32_t n, uint32_t n_steps,
+                                 uint32_t n_uregs, SkipPublished pub, bool option_skip_lists, bool option_fuse, bool program_eligible,
+                                 FuseLimits lim = FuseLimits()) {
+    if (!facts.eligible || !option_skip_lists || !option_fuse || !program_eligible || n == 0u) return 0u;
+    const uint32_t cap = fused_span_cap(n, n_uregs, lim);
+    const uint32_t most = n_steps < cap ? n_steps : cap;
+    if (most < 2u) return 0u;
+    SkipHistory trial = h, reached = h;
+    uint32_t s = 0;
+    for (; s < most; ++s) {
+        if (!prove_skip_lists(facts, trial, frame_no + s, inst + (size_t)s * n, n, pub, true)) break;
+        reached = trial;
+    }
+    if (s < 2u) return 0u;
+    h = reached;
+    return s;
 }
 
 // ---- ribbon effects: what the host can prove about the order of the alive list ---------------------------------------------------------

@@ -28,11 +28,13 @@ ABI_SYMBOLS = [
     "hnb_ctx_profile_marker", "hnb_program_kernel_timing",
     "hnb_comm_create_local", "hnb_comm_unique_id", "hnb_comm_create_rank", "hnb_comm_allreduce_alive", "hnb_comm_destroy", "hnb_comm_set_library",
     "hnb_effect_device_view", "hnb_effect_materialise", "hnb_jit_precompile_set", "hnb_effect_check", "hnb_effect_compare", "hnb_comm_describe", "hnb_program_device_view",
+    "hnb_simulate_steps", "hnb_effect_set_frames_ahead", "hnb_program_set_frames_ahead", "hnb_ctx_step_stats",
 ]
 
 # hnb_ctx_set_option (include/hanabi_amd.h): name -> option id
 OPTIONS = {"list_order": 1, "alternate": 2, "skip_lists": 3, "age_cohort": 4, "cull_lifetime": 5, "horizon": 6, "transpose": 7, "scene_merge": 8,
-           "suffix_proof": 9, "overlap_updates": 10, "stream_hints": 11, "set_module": 12, "jit_async": 13, "test_break_proof": 15, "ring_lists": 16, "slot_init": 17, "direct_upload": 18}
+           "suffix_proof": 9, "overlap_updates": 10, "stream_hints": 11, "set_module": 12, "jit_async": 13, "test_break_proof": 15, "ring_lists": 16, "slot_init": 17, "direct_upload": 18, "fuse_steps": 19}
+MAX_FUSED_STEPS = 8   # HNB_MAX_FUSED_STEPS
 SET_MODULE_OFF, SET_MODULE_CACHED, SET_MODULE_COMPILE, SET_MODULE_BACKGROUND = 0, 1, 2, 3
 
 
@@ -54,6 +56,14 @@ class EffectMetadata(C.Structure):
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
+class StepStats(C.Structure):
+    """HnbStepStats (hnb_ctx_step_stats): what the context has submitted since it was created."""
+    _fields_ = [(n, C.c_uint64) for n in ("frames", "fused_frames", "fused_launches", "update_launches", "list_launches")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
 class DeviceMeta(C.Structure):
@@ -167,6 +177,10 @@ def load_library():
         lib.hnb_program_kernel_info.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
         lib.hnb_jit_precompile.argtypes = [C.c_char_p, C.c_size_t]
         lib.hnb_jit_precompile_set.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_uint32]
+        lib.hnb_simulate_steps.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(SimParams)]
+        lib.hnb_effect_set_frames_ahead.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.hnb_program_set_frames_ahead.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.hnb_ctx_step_stats.argtypes = [C.c_void_p, C.POINTER(StepStats)]
         _lib = lib
     return _lib
 
@@ -250,6 +264,28 @@ class Context:
 
     def simulate(self):
         _check(self._lib.hnb_simulate(self._h))
+
+    def simulate_steps(self, params_list):
+        """hnb_simulate_steps: one frame per element, in one call. An element is a SimParams, a delta time, or a tuple of
+        frame_begin's arguments (dt, time, ...). Per-effect inputs of the steps: Effect / Program.set_frames_ahead before the call."""
+        steps = []
+        for e in params_list:
+            if isinstance(e, SimParams):
+                steps.append(e)
+                continue
+            a = tuple(e) if isinstance(e, (tuple, list)) else (e,)
+            dt, time = a[0], (a[1] if len(a) > 1 else 0.0)
+            rest = list(a[2:]) + [None] * (6 - len(a))
+            steps.append(SimParams(dt, time, dt if rest[0] is None else rest[0], time if rest[1] is None else rest[1],
+                                   dt if rest[2] is None else rest[2], time if rest[3] is None else rest[3]))
+        arr = (SimParams * max(len(steps), 1))(*steps)
+        _check(self._lib.hnb_simulate_steps(self._h, len(steps), arr))
+
+    def step_stats(self):
+        """hnb_ctx_step_stats: frames, fused_frames, fused_launches, update_launches, list_launches since the context was created."""
+        s = StepStats()
+        _check(self._lib.hnb_ctx_step_stats(self._h, C.byref(s)))
+        return s.as_dict()
 
     def enable_kernel_timing(self, every_n_frames=1):
         """0/False = off; n = bracket the kernels of every n-th simulated frame with HIP events."""
@@ -343,6 +379,15 @@ class Program:
         xf = None if transforms is None else np.ascontiguousarray(transforms, dtype=np.float32).reshape(len(sc), 12)
         _check(self._lib.hnb_program_set_frames(self._h, int(first), len(sc), sc.ctypes.data, sd.ctypes.data, None if xf is None else xf.ctypes.data))
 
+    def set_frames_ahead(self, spawn_counts, seeds, transforms=None, first=0):
+        """Inputs of the next Context.simulate_steps for instances [first, first + count): arrays [n_steps][count] (transforms [n_steps][count][12])."""
+        sc = np.ascontiguousarray(spawn_counts, dtype=np.uint32)
+        sd = np.ascontiguousarray(seeds, dtype=np.uint32)
+        assert sc.ndim == 2 and sc.shape == sd.shape
+        n_steps, count = sc.shape
+        xf = None if transforms is None else np.ascontiguousarray(transforms, dtype=np.float32).reshape(n_steps, count, 12)
+        _check(self._lib.hnb_program_set_frames_ahead(self._h, int(first), count, n_steps, sc.ctypes.data, sd.ctypes.data, None if xf is None else xf.ctypes.data))
+
     def kernel_timing(self):
         """Context.kernel_timing() restricted to this program's kernels."""
         u, c, i, n = C.c_double(), C.c_double(), C.c_double(), C.c_uint32()
@@ -407,6 +452,14 @@ class Effect:
         if transform is not None:
             xf = np.ascontiguousarray(np.asarray(transform, dtype=np.float32).reshape(12))
         _check(self._lib.hnb_effect_set_frame(self._h, int(spawn_count), int(seed) & 0xFFFFFFFF, None if xf is None else xf.ctypes.data))
+
+    def set_frames_ahead(self, spawn_counts, seeds, transforms=None):
+        """Inputs of the steps of the next Context.simulate_steps: one spawn count and seed (and 3x4 transform) per step."""
+        sc = np.ascontiguousarray(spawn_counts, dtype=np.uint32)
+        sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64) & 0xFFFFFFFF, dtype=np.uint32)
+        assert sc.ndim == 1 and sc.shape == sd.shape
+        xf = None if transforms is None else np.ascontiguousarray(transforms, dtype=np.float32).reshape(len(sc), 12)
+        _check(self._lib.hnb_effect_set_frames_ahead(self._h, len(sc), sc.ctypes.data, sd.ctypes.data, None if xf is None else xf.ctypes.data))
 
     def set_property(self, name, values):
         v = np.atleast_1d(np.asarray(values))

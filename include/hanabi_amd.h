@@ -362,6 +362,13 @@ int hnb_ctx_synchronize(HnbContext* ctx);
 #define HNB_SET_MODULE_CACHED 1u
 #define HNB_SET_MODULE_COMPILE 2u
 #define HNB_SET_MODULE_BACKGROUND 3u
+/* HNB_OPT_FUSE_STEPS (default 1; from the next hnb_simulate_steps on): a program for which the host can prove that the next S >= 2 steps of the call
+ *   neither spawn nor lose a particle runs them in ONE launch of its streaming update kernel: planes loaded once, the update program run S times in
+ *   registers with each step's parameter block, planes stored once (DESIGN.md "Several frames in one launch"). 0: hnb_simulate_steps enqueues plain
+ *   single frames. Same results bit for bit with either value: it exists for A/B runs and tests. */
+#define HNB_OPT_FUSE_STEPS 19u
+/* Longest span of frames one launch covers; longer provable spans are split. */
+#define HNB_MAX_FUSED_STEPS 8u
 int hnb_ctx_set_option(HnbContext* ctx, uint32_t option, uint32_t value);
 
 /* Replaces EffectShaderSources::generate + pipeline specialisation (src/lib.rs:805-1336). */
@@ -407,6 +414,37 @@ int hnb_effect_set_property(HnbEffect* fx, const char* name, const void* value, 
  * init -> (indirect/prefix-sum folded) -> update+kill+compaction. Replaces `simulate`
  * (src/render/mod.rs:6942-7613). Asynchronous. */
 int hnb_simulate(HnbContext* ctx);
+
+/* Enqueue `n_steps` frames in one call: a fixed-timestep host catching up, a pre-roll, a headless host stepping as fast as it can.
+ * The state afterwards - every plane, both list columns, the dead list, the counters, `fault`, the event buffers - is bit for bit the state after
+ *     for (s = 0; s < n_steps; ++s) { hnb_frame_begin(ctx, &params[s]); <per-effect inputs of step s>; hnb_simulate(ctx); }
+ * Asynchronous like hnb_simulate. n_steps == 0: HNB_OK, nothing happens (params may be NULL). n_steps == 1: exactly hnb_frame_begin + hnb_simulate.
+ * Per-effect inputs of the steps are given BEFORE the call with the array forms below. An effect that was not given inputs for a step behaves in it
+ * as in a frame without hnb_effect_set_frame: it spawns nothing, and keeps the seed and the transform it had (a request made with
+ * hnb_effect_set_frame / hnb_program_set_frames before the call is consumed by step 0). Properties and hnb_effect_set_simulated hold for the whole
+ * call. After the call an effect's seed and transform are those of its last step with inputs.
+ * With HNB_OPT_FUSE_STEPS (the default) programs whose steps provably neither spawn nor lose a particle run up to HNB_MAX_FUSED_STEPS of them per
+ * launch: streamable update stacks with a pre-built kernel (hnb_program_kernel_info: "aot-stream"), reaped by lifetime only, without ribbons, spawn
+ * events or a parent, of more than 65,536 slots over their instances. Every other program - and every step that cannot be proven - runs as a single
+ * frame inside the call; so do all steps while kernel timing is enabled. Programs of one context may thus advance at different granularity inside
+ * the call; nothing outside it can tell. */
+int hnb_simulate_steps(HnbContext* ctx, uint32_t n_steps, const HnbSimParams* params /* [n_steps] */);
+/* Inputs of the steps of the NEXT hnb_simulate_steps, step s = element s: hnb_effect_set_frame / hnb_program_set_frames with one more dimension.
+ * transforms3x4: n_steps x 12 floats, or NULL (the transform stays). The program form takes step-major arrays: element [s * count + i] belongs to
+ * step s of instance first + i (transforms: 12 floats each). Steps past n_steps get no inputs. The arrays are copied. A plain hnb_simulate, or
+ * the end of the hnb_simulate_steps that used them, drops them. */
+int hnb_effect_set_frames_ahead(HnbEffect* fx, uint32_t n_steps, const uint32_t* spawn_counts, const uint32_t* seeds, const float* transforms3x4);
+int hnb_program_set_frames_ahead(HnbProgram* prog, uint32_t first, uint32_t count, uint32_t n_steps, const uint32_t* spawn_counts, const uint32_t* seeds,
+                                 const float* transforms3x4);
+/* What the context has submitted since it was created (host-side counters, no synchronisation). */
+typedef struct HnbStepStats {
+    uint64_t frames;           /* simulated frames of the context (hnb_simulate calls + steps of hnb_simulate_steps) */
+    uint64_t fused_frames;     /* frames of a program that ran inside a launch covering several (summed over programs) */
+    uint64_t fused_launches;   /* such launches */
+    uint64_t update_launches;  /* update kernels launched: per-program ones (fused or not) and the shared launches of small programs */
+    uint64_t list_launches;    /* list-maintenance kernels launched (row counting, compaction, slot-order rebuild; shared ones included) */
+} HnbStepStats;
+int hnb_ctx_step_stats(HnbContext* ctx, HnbStepStats* out);
 
 /* ---- Device-side output -------------------------------------------------------------------------------------------------------
  * Where the reference's hot path ENDS: GPU-resident buffers the next stage binds directly - the particle buffer, the indirect index
