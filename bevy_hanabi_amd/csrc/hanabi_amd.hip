@@ -169,13 +169,18 @@ struct JitJob {
     std::vector<HnbAttrEntry> attrs;
     bool streams = false, aot_static = false;
     ProgramOptions opt;
+    // ... or, steps: the steps module of the program (HnbProgram::steps_ops / steps_waves / steps_cohort) instead
+    bool steps = false;
+    std::vector<Ins> steps_ops;
+    int steps_waves = 0;
+    bool steps_cohort = false;
     jit::Result res;
     bool ok = false;
 };
 struct JitWorker {
     std::thread thread;
     std::mutex mu;
-    std::condition_variable cv;
+    std::condition_variable cv, done_cv;   // work for the thread / a job has finished (hnb_program_prepare_steps waits for its program's)
     std::deque<std::unique_ptr<JitJob>> queue, done;
     bool stop = false;
     uint32_t in_flight = 0;   // queued or compiling
@@ -287,6 +292,18 @@ struct HnbProgram {
     uint64_t serial = 0;            // identity across destruction (HNB_OPT_JIT_ASYNC: a finished compilation looks its program up by it)
     bool jit_pending = false;
     std::string kernel_info, jit_log;
+    // hnb_simulate_steps for a specialised streaming update (jit_update): the FUSED instantiation lives in a module of its own (jit::build_steps), built
+    // the first time it can matter (request_steps_kernel) or on demand (hnb_program_prepare_steps). steps_ops: the update stream it is generated from,
+    // kept only for programs whose single-frame stream kernel is specialised at run time (empty: there is never a steps module)
+    enum class StepsState { NotRequested, Built, Pending, Failed };
+    hipModule_t steps_module = nullptr;
+    hipFunction_t steps_update = nullptr;
+    StepsState steps_state = StepsState::NotRequested;
+    bool steps_from_cache = false;
+    std::string steps_why;          // Failed: the reason, one line (the whole log is in jit_log)
+    std::vector<Ins> steps_ops;
+    int steps_waves = 0;
+    bool steps_cohort = false;
     // what a set module generates this program's cases from (narrow register file only; empty: never a member), and its case in the loaded module
     std::vector<Ins> h_init, h_update;
     std::string set_sig;
@@ -913,6 +930,79 @@ void install_program_jit(HnbProgram* p, const jit::Result& res) {
     if (res.from_cache) p->kernel_info += " (jit cache hit)";
 }
 
+// The steps module of a program whose streaming update is specialised at run time (hnb_jit.h "steps modules"): the same op sequence, wave budget and
+// cohort choice as the single-frame kernel of make_jit_request
+jit::Request make_steps_request(const std::vector<Ins>& ops, int waves, bool cohort) {
+    jit::Request rq;
+    rq.update = ops.data(); rq.update_len = (uint32_t)ops.size();
+    rq.want_update_stream = !ops.empty();
+    rq.stream_waves = waves;
+    rq.stream_cohort = cohort;
+    return rq;
+}
+void steps_build_failed(HnbProgram* p, const std::string& log) {   // tried once: single frames inside hnb_simulate_steps from now on
+    p->steps_state = HnbProgram::StepsState::Failed;
+    p->steps_why = log.substr(0, log.find('\n'));
+    if (p->steps_why.empty()) p->steps_why = "no log";
+    p->jit_log = "steps kernel: " + log;
+}
+void install_program_steps(HnbProgram* p, const jit::Result& res) {
+    hipModule_t mod = nullptr;
+    hipFunction_t fu = nullptr;
+    hipError_t je = hipModuleLoadData(&mod, res.code.data());
+    if (je == hipSuccess) je = hipModuleGetFunction(&fu, mod, res.update_name.c_str());
+    if (je != hipSuccess) {
+        if (mod) hipModuleUnload(mod);
+        (void)hipGetLastError();
+        steps_build_failed(p, std::string("loading the code object failed: ") + hipGetErrorString(je));
+        return;
+    }
+    p->steps_module = mod; p->steps_update = fu;
+    p->steps_from_cache = res.from_cache;
+    p->steps_state = HnbProgram::StepsState::Built;
+}
+// What never changes about "this program can run fused spans on a steps module" (fuse_candidate adds the context's options and the slot count)
+const char* steps_never_reason(const HnbProgram* p) {
+    if (!p->update_streams) return "never fuses: not a macro-op update";
+    if (!p->skip_facts.eligible) return "never fuses: particles can die by more than their lifetime, or the program is linked to others";
+    if (p->has_ribbons || p->hdr.n_event_channels != 0u) return "never fuses: ribbons or spawn events";
+    if (p->stream_launch_fused) return "pre-built fused kernel";
+    if (p->steps_ops.empty()) return "never fuses: the update is not specialised (HNB_JIT=0)";
+    return nullptr;
+}
+void jit_worker_main(JitWorker* w);
+void queue_jit_job(HnbContext* ctx, std::unique_ptr<JitJob> job) {   // HNB_OPT_JIT_ASYNC: onto the context's compilation thread, started with its first job
+    if (!ctx->jit_worker) {
+        ctx->jit_worker.reset(new JitWorker());
+        ctx->jit_worker->thread = std::thread(jit_worker_main, ctx->jit_worker.get());
+    }
+    {
+        std::lock_guard<std::mutex> lk(ctx->jit_worker->mu);
+        ctx->jit_worker->queue.push_back(std::move(job));
+        ctx->jit_worker->in_flight += 1;
+    }
+    ctx->jit_worker->cv.notify_one();
+}
+// Build (or queue, HNB_OPT_JIT_ASYNC unless `wait`) the steps module of a program that has none and could use one. The single-frame kernel must be
+// installed: while it is pending, or if it failed, the interpreter runs and there is nothing to fuse.
+void request_steps_kernel(HnbContext* ctx, HnbProgram* p, bool wait) {
+    if (p->steps_state != HnbProgram::StepsState::NotRequested || !p->jit_update || steps_never_reason(p)) return;
+    const bool async = ctx->jit_async && !wait;
+    jit::Result res;
+    if (jit::build_steps(make_steps_request(p->steps_ops, p->steps_waves, p->steps_cohort), res, /*cache_only=*/async)) {
+        install_program_steps(p, res);
+    } else if (async && res.log.empty()) {
+        std::unique_ptr<JitJob> job(new JitJob());
+        job->program_serial = p->serial;
+        job->steps = true;
+        job->steps_ops = p->steps_ops; job->steps_waves = p->steps_waves; job->steps_cohort = p->steps_cohort;
+        queue_jit_job(ctx, std::move(job));
+        p->steps_state = HnbProgram::StepsState::Pending;
+    } else {
+        steps_build_failed(p, res.log);
+    }
+}
+
 // HNB_OPT_JIT_ASYNC: the context's compilation thread (JitWorker)
 void jit_worker_main(JitWorker* w) {
     for (;;) {
@@ -924,10 +1014,17 @@ void jit_worker_main(JitWorker* w) {
             job = std::move(w->queue.front());
             w->queue.pop_front();
         }
-        const jit::Request rq = make_jit_request(job->blob.data(), job->hdr, job->attrs.data(), job->streams, job->aot_static, job->opt);
-        job->ok = jit::build(rq, job->res);
-        std::lock_guard<std::mutex> lk(w->mu);
-        w->done.push_back(std::move(job));
+        if (job->steps) {
+            job->ok = jit::build_steps(make_steps_request(job->steps_ops, job->steps_waves, job->steps_cohort), job->res);
+        } else {
+            const jit::Request rq = make_jit_request(job->blob.data(), job->hdr, job->attrs.data(), job->streams, job->aot_static, job->opt);
+            job->ok = jit::build(rq, job->res);
+        }
+        {
+            std::lock_guard<std::mutex> lk(w->mu);
+            w->done.push_back(std::move(job));
+        }
+        w->done_cv.notify_all();
     }
 }
 // ... and hnb_simulate's side of it: what has been compiled since the last frame goes into the programs that still exist. The kernels it
@@ -945,6 +1042,11 @@ void install_finished_jit(HnbContext* ctx) {
         for (HnbProgram* q : ctx->programs)
             if (q->serial == j->program_serial) p = q;
         if (!p) continue;   // destroyed in the meantime
+        if (j->steps) {     // (a launch of its own kind: nothing in flight uses it yet)
+            if (j->ok) install_program_steps(p, j->res);
+            else steps_build_failed(p, j->res.log);
+            continue;
+        }
         p->jit_pending = false;
         if (j->ok) install_program_jit(p, j->res);
         else if (!j->res.log.empty()) p->jit_log = j->res.log;
@@ -1145,25 +1247,20 @@ int hnb_program_create(HnbContext* ctx, const void* blob, size_t blob_size, HnbP
     p->serial = ctx->next_program_serial++;
     if (jit::enabled()) {
         const jit::Request rq = make_jit_request(b, h, p->attrs.data(), p->update_streams, aot_static, ctx->popt);
+        if (rq.want_update_stream) {   // what a steps module of this program would be generated from (request_steps_kernel)
+            p->steps_ops.assign(rq.update, rq.update + rq.update_len);
+            p->steps_waves = rq.stream_waves; p->steps_cohort = rq.stream_cohort;
+        }
         jit::Result res;
         if (jit::build(rq, res, /*cache_only=*/ctx->jit_async)) {
             install_program_jit(p, res);
         } else if (ctx->jit_async && res.log.empty() && (rq.want_init || rq.want_update_generic || rq.want_update_stream)) {
             // not in the cache: the ahead-of-time / interpreter kernels run until the context's compilation thread has the program's own
-            if (!ctx->jit_worker) {
-                ctx->jit_worker.reset(new JitWorker());
-                ctx->jit_worker->thread = std::thread(jit_worker_main, ctx->jit_worker.get());
-            }
             std::unique_ptr<JitJob> job(new JitJob());
             job->program_serial = p->serial;
             job->blob.assign(b, b + blob_size);
             job->hdr = h; job->attrs = p->attrs; job->streams = p->update_streams; job->aot_static = aot_static; job->opt = ctx->popt;
-            {
-                std::lock_guard<std::mutex> lk(ctx->jit_worker->mu);
-                ctx->jit_worker->queue.push_back(std::move(job));
-                ctx->jit_worker->in_flight += 1;
-            }
-            ctx->jit_worker->cv.notify_one();
+            queue_jit_job(ctx, std::move(job));
             p->jit_pending = true;
         } else if (!res.log.empty()) {
             p->jit_log = res.log;
@@ -1275,6 +1372,7 @@ int hnb_program_destroy(HnbProgram* p) {
     while (!p->effects.empty()) hnb_effect_destroy(p->effects.back());
     free_tables(p);
     if (p->jit_module) hipModuleUnload(p->jit_module);
+    if (p->steps_module) hipModuleUnload(p->steps_module);
     for (auto& blk : p->slab_blocks) hipFree(blk.base);
     hipFree(p->d_plane_by_attr);
     hipFree(p->d_code);
@@ -2238,7 +2336,10 @@ static int enqueue_program_update(HnbContext* ctx, HnbProgram* p, hipStream_t st
         ctx->step_stats.update_launches += 1;
         if (p->fuse_span >= 2u) {   // frames F .. F + span - 1 of this program in one launch (hnb_simulate_steps)
             sa.fuse_steps = p->fuse_span;
-            p->stream_launch_fused(total_chunks, st, sa, p->d_inst_base, dfi, dub, cb);
+            if (p->steps_update) {   // (a program specialised at run time: its steps module, on the argument block of its single-frame launch below)
+                void* ka[] = {&sa, &p->d_inst_base, &dfi, &dub, &cb};
+                HIP_TRY(hipModuleLaunchKernel(p->steps_update, total_chunks, 1, 1, kBlock, 1, 1, 0, st, ka, nullptr));
+            } else p->stream_launch_fused(total_chunks, st, sa, p->d_inst_base, dfi, dub, cb);
             ctx->step_stats.fused_launches += 1;
             ctx->step_stats.fused_frames += p->fuse_span;
             p->fused_frames += p->fuse_span;
@@ -2436,7 +2537,8 @@ static bool fuse_candidate(const HnbContext* ctx, const HnbProgram* p) {
     const uint64_t chunks = (uint64_t)p->effects.size() * p->dev.chunks_per_inst;
     return ctx->fuse_steps && ctx->skip_lists && !ctx->break_proof && ctx->timing == 0u &&      // (kernel timing: one launch per frame stays attributable; the test hook claims without proof)
            p->fused_left == 0u && p->update_streams && p->skip_facts.eligible && !p->has_ribbons && p->hdr.n_event_channels == 0u &&
-           p->stream_launch_fused && !p->jit_update && !p->jit_pending &&                       // a pre-built op sequence (the kernels specialised at run time have no fused form)
+           ((p->stream_launch_fused && !p->jit_update && !p->jit_pending) ||                    // a pre-built op sequence ...
+            (p->jit_update && p->steps_update)) &&                                              // ... or a kernel specialised at run time whose steps module is installed
            chunks > kSceneMaxChunks;                                                            // never a candidate for the merged launches / set modules: its own launch
 }
 // params / first_step: the steps still to run, and the index of the first of them inside the call (the effects' ahead inputs are indexed by it)
@@ -2494,6 +2596,18 @@ int hnb_simulate_steps(HnbContext* ctx, uint32_t n_steps, const HnbSimParams* pa
             for (size_t i = 0; i < p->effects.size(); ++i)
                 if (!p->effects[i]->parent)
                     return fail(HNB_ERR_INVALID_ARG, "effect #%zu reads its parent particle (InheritAttributeModifier / parent_attr) but has no parent: call hnb_effect_set_parent", i);
+    if (n_steps >= 2u) {
+        // a program specialised at run time gets its steps module the first time it can matter: the static part of fuse_candidate holds. Built here
+        // (a cache hit is a file read, a miss one compilation), or queued under HNB_OPT_JIT_ASYNC: single frames until install_finished_jit has it
+        HIP_TRY(hipSetDevice(ctx->device));
+        install_finished_jit(ctx);
+        for (HnbProgram* p : ctx->programs) {
+            if (p->steps_state != HnbProgram::StepsState::NotRequested || !p->jit_update || !ctx->fuse_steps) continue;
+            bool parent = false;
+            for (const HnbEffect* fx : p->effects) parent = parent || fx->parent != nullptr;
+            if (!parent && (uint64_t)p->effects.size() * p->dev.chunks_per_inst > kSceneMaxChunks) request_steps_kernel(ctx, p, false);
+        }
+    }
     int rc = HNB_OK;
     for (uint32_t s = 0; s < n_steps && rc == HNB_OK; ++s) {
         ctx->sim = params[s];
@@ -2842,6 +2956,16 @@ int hnb_program_kernel_info(HnbProgram* prog, char* buf, size_t buf_size) {
     std::string s = prog->kernel_info;
     if (prog->jit_pending) s += " (specialisation pending: HNB_OPT_JIT_ASYNC)";
     if (!prog->jit_log.empty()) s += "\njit log: " + prog->jit_log;
+    {   // the steps module (hnb_simulate_steps for an update specialised at run time)
+        const char* never = steps_never_reason(prog);
+        s += "\nsteps kernel: ";
+        switch (prog->steps_state) {
+        case HnbProgram::StepsState::NotRequested: s += std::string("not requested") + (never ? std::string(" (") + never + ")" : std::string()); break;
+        case HnbProgram::StepsState::Built: s += std::string("built") + (prog->steps_from_cache ? " (jit cache hit)" : ""); break;
+        case HnbProgram::StepsState::Pending: s += "pending (HNB_OPT_JIT_ASYNC)"; break;
+        case HnbProgram::StepsState::Failed: s += "failed: " + prog->steps_why; break;
+        }
+    }
     if (!prog->dev.age_cohort && prog->dev.cull_lifetime && prog->age_cohort_mode == HNB_AGE_COHORT_AUTO && (prog->hdr.render_reads_lo >> HNB_ATTR_AGE & 1u))
         s += "\nage cohorts: off (HNB_AGE_COHORT_AUTO: the asset's render modifiers read AGE after every frame)";
     if (prog->dev.age_cohort) {   // (debug statistics: synchronises and reads the per-chunk state words of every instance)
@@ -2895,6 +3019,41 @@ int hnb_jit_precompile(const void* blob, size_t blob_size) {
     if (!rq.want_init && !rq.want_update_generic && !rq.want_update_stream) return HNB_OK;
     jit::Result res;
     if (!jit::build(rq, res)) return fail(HNB_ERR_BAD_PROGRAM, "kernel specialisation failed: %s", res.log.c_str());
+    return HNB_OK;
+}
+
+int hnb_jit_precompile_steps(const void* blob, size_t blob_size) {
+    HnbProgramHeader h;
+    int rc = validate_blob(blob, blob_size, &h);
+    if (rc != HNB_OK) return rc;
+    const uint8_t* b = static_cast<const uint8_t*>(blob);
+    std::vector<HnbAttrEntry> attrs(h.n_attrs);
+    memcpy(attrs.data(), b + h.attrs_off, h.n_attrs * sizeof(HnbAttrEntry));
+    if (!update_is_streamable(b, h, attrs.data())) return HNB_OK;
+    StreamLaunchFn fn = nullptr, fused = nullptr;
+    const char* name = "";
+    select_stream_kernel(reinterpret_cast<const Ins*>(b + h.update_off), h.update_len, &fn, &name, &fused);
+    const jit::Request rq = make_jit_request(b, h, attrs.data(), true, strcmp(name, "ProgInterp") != 0, ProgramOptions());   // (the default options, as hnb_jit_precompile)
+    if (!rq.want_update_stream) return HNB_OK;   // (a pre-built sequence: its fused form is in the library)
+    jit::Result res;
+    if (!jit::build_steps(rq, res)) return fail(HNB_ERR_BAD_PROGRAM, "steps kernel: specialisation failed: %s", res.log.c_str());
+    return HNB_OK;
+}
+
+int hnb_program_prepare_steps(HnbProgram* prog) {
+    if (!prog) return fail(HNB_ERR_INVALID_ARG, "prog is NULL");
+    HnbContext* ctx = prog->ctx;
+    if (steps_never_reason(prog)) return HNB_OK;   // (hnb_program_kernel_info says which)
+    HIP_TRY(hipSetDevice(ctx->device));
+    // HNB_OPT_JIT_ASYNC: what the compilation thread still owes this program - its own module, a steps module queued by an earlier call - is waited for
+    for (;;) {
+        install_finished_jit(ctx);
+        if (!prog->jit_pending && prog->steps_state != HnbProgram::StepsState::Pending) break;
+        std::unique_lock<std::mutex> lk(ctx->jit_worker->mu);
+        ctx->jit_worker->done_cv.wait(lk, [&] { return !ctx->jit_worker->done.empty(); });
+    }
+    request_steps_kernel(ctx, prog, /*wait=*/true);
+    if (prog->steps_state == HnbProgram::StepsState::Failed) return fail(HNB_ERR_BAD_PROGRAM, "steps kernel: %s", prog->steps_why.c_str());
     return HNB_OK;
 }
 

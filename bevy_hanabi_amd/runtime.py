@@ -29,6 +29,7 @@ ABI_SYMBOLS = [
     "hnb_comm_create_local", "hnb_comm_unique_id", "hnb_comm_create_rank", "hnb_comm_allreduce_alive", "hnb_comm_destroy", "hnb_comm_set_library",
     "hnb_effect_device_view", "hnb_effect_materialise", "hnb_jit_precompile_set", "hnb_effect_check", "hnb_effect_compare", "hnb_comm_describe", "hnb_program_device_view",
     "hnb_simulate_steps", "hnb_effect_set_frames_ahead", "hnb_program_set_frames_ahead", "hnb_ctx_step_stats",
+    "hnb_program_prepare_steps", "hnb_jit_precompile_steps",
 ]
 
 # hnb_ctx_set_option (include/hanabi_amd.h): name -> option id
@@ -181,6 +182,8 @@ def load_library():
         lib.hnb_effect_set_frames_ahead.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.hnb_program_set_frames_ahead.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.hnb_ctx_step_stats.argtypes = [C.c_void_p, C.POINTER(StepStats)]
+        lib.hnb_program_prepare_steps.argtypes = [C.c_void_p]
+        lib.hnb_jit_precompile_steps.argtypes = [C.c_char_p, C.c_size_t]
         _lib = lib
     return _lib
 
@@ -198,6 +201,12 @@ def validate_program(blob: bytes):
 def jit_precompile(blob: bytes):
     """Compile and cache the kernels specialised for this program (hiprtc; needs no GPU)."""
     _check(load_library().hnb_jit_precompile(blob, len(blob)))
+
+
+def jit_precompile_steps(blob: bytes):
+    """Compile and cache the steps kernel of this program (the several-frames form of a streaming update specialised at run time:
+    Program.prepare_steps; needs no GPU). Writes nothing for a program without such an update."""
+    _check(load_library().hnb_jit_precompile_steps(blob, len(blob)))
 
 
 def jit_precompile_set(blobs):
@@ -405,6 +414,11 @@ class Program:
         buf = C.create_string_buffer(4096)
         _check(self._lib.hnb_program_kernel_info(self._h, buf, len(buf)))
         return buf.value.decode()
+
+    def prepare_steps(self):
+        """hnb_program_prepare_steps: build and install the steps kernel of a 'jit-stream' program now (Context.simulate_steps fuses its provable
+        spans from the first call on). Does nothing for programs with a pre-built fused kernel or that can never fuse: see kernel_info()."""
+        _check(self._lib.hnb_program_prepare_steps(self._h))
 
     def destroy(self):
         if self._h:

@@ -424,11 +424,19 @@ int hnb_simulate(HnbContext* ctx);
  * hnb_effect_set_frame / hnb_program_set_frames before the call is consumed by step 0). Properties and hnb_effect_set_simulated hold for the whole
  * call. After the call an effect's seed and transform are those of its last step with inputs.
  * With HNB_OPT_FUSE_STEPS (the default) programs whose steps provably neither spawn nor lose a particle run up to HNB_MAX_FUSED_STEPS of them per
- * launch: streamable update stacks with a pre-built kernel (hnb_program_kernel_info: "aot-stream"), reaped by lifetime only, without ribbons, spawn
+ * launch: streamable update stacks with a pre-built kernel (hnb_program_kernel_info: "aot-stream") or one specialised at run time ("jit-stream",
+ * once its steps kernel is installed: hnb_program_prepare_steps), reaped by lifetime only, without ribbons, spawn
  * events or a parent, of more than 65,536 slots over their instances. Every other program - and every step that cannot be proven - runs as a single
  * frame inside the call; so do all steps while kernel timing is enabled. Programs of one context may thus advance at different granularity inside
  * the call; nothing outside it can tell. */
 int hnb_simulate_steps(HnbContext* ctx, uint32_t n_steps, const HnbSimParams* params /* [n_steps] */);
+/* A "jit-stream" program runs fused spans on a STEPS KERNEL: the several-frames form of its specialised update, a hiprtc module of its own that is
+ * built the first time it can matter - the first hnb_simulate_steps of two or more steps in which the program could fuse: a file read on a cache hit,
+ * one compilation otherwise (with HNB_OPT_JIT_ASYNC on the context's compilation thread; single frames until it is installed). This call builds and
+ * installs it NOW instead - at load time, not in the first stepping call -, and waits for whatever specialisation of the program HNB_OPT_JIT_ASYNC
+ * still has in flight. HNB_OK and nothing done for a program that has a pre-built fused kernel or can never fuse; an error if the compilation fails
+ * (tried once: the program then runs single frames inside hnb_simulate_steps). hnb_program_kernel_info's "steps kernel:" line tells the state. */
+int hnb_program_prepare_steps(HnbProgram* prog);
 /* Inputs of the steps of the NEXT hnb_simulate_steps, step s = element s: hnb_effect_set_frame / hnb_program_set_frames with one more dimension.
  * transforms3x4: n_steps x 12 floats, or NULL (the transform stays). The program form takes step-major arrays: element [s * count + i] belongs to
  * step s of instance first + i (transforms: 12 floats each). Steps past n_steps get no inputs. The arrays are copied. A plain hnb_simulate, or
@@ -580,7 +588,8 @@ int hnb_effect_compare(HnbEffect* a, HnbEffect* b, HnbEffectDiff* out);
 int hnb_effect_sort_ribbons(HnbEffect* fx);
 
 /* Which kernels run this program, as text: "init=jit|interp|none update=aot-stream:<name>|jit-stream|
- * jit-generic|interp-stream|interp-generic", followed by the specialisation log if it failed.
+ * jit-generic|interp-stream|interp-generic", followed by the specialisation log if it failed and by
+ * "steps kernel: not requested|built|pending|failed: <why>" (hnb_program_prepare_steps).
  * At creation the library specialises the kernels a program would otherwise interpret (the
  * counterpart of the reference compiling generated WGSL per effect, src/lib.rs:805-1336) with
  * hiprtc; HNB_JIT=0 in the environment keeps the interpreter kernels, HNB_JIT_CACHE=<dir> moves the
@@ -588,6 +597,9 @@ int hnb_effect_sort_ribbons(HnbEffect* fx);
 int hnb_program_kernel_info(HnbProgram* prog, char* buf, size_t buf_size);
 /* Compile and cache the specialised kernels of a program blob. Needs no device (build boxes). */
 int hnb_jit_precompile(const void* blob, size_t blob_size);
+/* Compile and cache the STEPS KERNEL (hnb_program_prepare_steps) of a program blob: a cache entry of its own, beside the one of hnb_jit_precompile.
+ * HNB_OK and no entry for a blob whose update is not a streaming one specialised at run time. Needs no device. */
+int hnb_jit_precompile_steps(const void* blob, size_t blob_size);
 /* Compile and cache the SET MODULE (HNB_OPT_SET_MODULE) of the given program blobs: what a context that holds exactly these programs as its
  * small effects looks up. Order and duplicates do not matter; blobs that can never join a merged launch are skipped as hnb_simulate skips them
  * (wide register file, capacity > 65,536, spawn events in or out). The runtime set also leaves out programs whose INSTANCES rule them out (more

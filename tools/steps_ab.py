@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""A/B of hnb_simulate_steps against single frames: c2 (effects.firework_trails, burst) at 16,777,216 particles under the library defaults.
+"""A/B of hnb_simulate_steps against single frames: c2 (effects.firework_trails, burst) at 16,777,216 particles under the library defaults,
+or with --asset tangent_drag a stack without a pre-built kernel (update=jit-stream: burst, lifetime uniform(2, 3), TangentAccel + LinearDrag),
+whose fused spans run on the steps kernel hiprtc builds for it.
 
 Per mode a fresh context plays the same script: the burst and 5 warm-up frames (not timed), then `--windows` windows of 32 simulated frames at a
 small dt (nobody dies: the c2 metric is defined on complete bursts), each window submitted as
@@ -32,13 +34,34 @@ def frame_seed(f):
     return oracle.pcg_hash(0xC0FFEE + f)
 
 
-def run_mode(mode, cap, windows, check, marker):
+def tangent_drag(cap):
+    """Burst on a sphere surface, tangential acceleration around Z and drag: the update of examples/portal.rs on a burst that lives 2 .. 3 s."""
     import bevy_hanabi_amd as bh
+    A, w = bh.Attribute, bh.ExprWriter()
+    init = [bh.SetPositionSphereModifier(w.lit((0.0, 0.0, 0.0)).expr(), w.lit(4.0).expr(), bh.ShapeDimension.Surface),
+            bh.SetAttributeModifier(A.VELOCITY, ((w.rand(bh.VectorType.VEC3F) * w.lit(2.0) - w.lit(1.0)) * w.lit(3.0)).expr()),
+            bh.SetAttributeModifier(A.AGE, w.lit(0.0).expr()),
+            bh.SetAttributeModifier(A.LIFETIME, w.lit(2.0).uniform(w.lit(3.0)).expr())]
+    update = [bh.TangentAccelModifier(w.lit((0.0, 0.0, 0.0)).expr(), w.lit((0.0, 0.0, 1.0)).expr(), w.lit(30.0).expr()), bh.LinearDragModifier(w.lit(2.0).expr())]
+    asset = bh.EffectAsset(cap, bh.SpawnerSettings.once(float(cap)), w.finish())
+    for m in init:
+        asset = asset.init(m)
+    for m in update:
+        asset = asset.update(m)
+    return asset
+
+
+def make_asset(name, cap):
     from bevy_hanabi_amd import effects
+    return {"c2": effects.firework_trails, "tangent_drag": tangent_drag}[name](cap)
+
+
+def run_mode(mode, cap, windows, check, marker, asset_name="c2"):
+    import bevy_hanabi_amd as bh
     total = 1 + WARM + 32 * windows
     dt = min(1 / 60, 0.5 / total)                 # 0.5 s of the 0.8 s the youngest particle lives: every span stays provable to the end
     ctx = bh.Context(0)
-    fx = ctx.create_program(bh.lower(effects.firework_trails(cap))).create_effect()
+    fx = ctx.create_program(bh.lower(make_asset(asset_name, cap))).create_effect()
     f = 0
     for _ in range(1 + WARM):
         ctx.frame_begin(dt, f * dt)
@@ -69,21 +92,20 @@ def run_mode(mode, cap, windows, check, marker):
     if hasattr(ctx, "step_stats"):
         out["step_stats"] = ctx.step_stats()
     if check:
-        out["slab"] = slab_check(fx, cap, f, dt)
+        out["slab"] = slab_check(fx, cap, f, dt, asset_name=asset_name)
     out["device_check"] = fx.check()
     ctx.close()
     return out
 
 
-def slab_check(fx, cap, frames, dt, slots=16384):
+def slab_check(fx, cap, frames, dt, slots=16384, asset_name="c2"):
     """Slots [B, B + S) of the effect against an oracle effect of capacity S and slot_base B fed the same frames: every stored plane and the set of
     alive slots, bit for bit (NaN == NaN)."""
     import bevy_hanabi_amd as bh
     import oracle
-    from bevy_hanabi_amd import effects
     S = min(slots, cap)
     B = min(cap // 2 // 4096 * 4096, cap - S)
-    asset = effects.firework_trails(S)
+    asset = make_asset(asset_name, S)
     o = oracle.OracleEffect(bh.serialize_asset(asset), B, omp=True)
     for f in range(frames):
         o.step(dt, S if f == 0 else 0, frame_seed(f), time=f * dt)
@@ -106,6 +128,7 @@ def slab_check(fx, cap, frames, dt, slots=16384):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--modes", default="a,b,c,d")
+    ap.add_argument("--asset", default="c2", choices=["c2", "tangent_drag"], help="c2: a pre-built stream kernel; tangent_drag: update=jit-stream")
     ap.add_argument("--capacity", type=int, default=1 << 24)
     ap.add_argument("--windows", type=int, default=12)
     ap.add_argument("--rounds", type=int, default=1, help="repeat the whole list of modes (alternation inside one process)")
@@ -117,7 +140,7 @@ def main():
     rows = []
     for r in range(args.rounds):
         for i, m in enumerate(args.modes.split(",")):
-            row = run_mode(m, args.capacity, args.windows, not args.no_check, 100 + i if args.markers else 0)
+            row = run_mode(m, args.capacity, args.windows, not args.no_check, 100 + i if args.markers else 0, args.asset)
             row["round"], row["label"] = r, args.label
             rows.append(row)
             ok = "slab ok" if row.get("slab", {}).get("ok") else ("slab NOT CHECKED" if "slab" not in row else "SLAB DIFFERS " + "; ".join(row["slab"]["problems"]))

@@ -35,6 +35,7 @@ def main():
     t0 = time.time()
     for a in assets:
         bh.jit_precompile(bh.lower(a))
+        bh.jit_precompile_steps(bh.lower(a))   # (an entry only for streamable stacks specialised at run time: their several-frames kernel)
     print(f"warm_jit_cache: {len(assets)} programs in {time.time() - t0:.1f} s")
     # Set modules (HNB_OPT_SET_MODULE): the scene of every single-entity example effect (bench.py's small_effects_scene, tests/test_scene_merge.py)
     # and the small sets of tests/test_set_module.py
