@@ -288,6 +288,7 @@ struct HnbProgram {
     bool slot_init_eligible = false;   // the init reads neither PARTICLE_COUNTER nor a parent particle, no ribbons: large spawns may run slot-major (plan::plan_slot_init)
     uint32_t slot_init_frames = 0;     // statistics
     uint32_t sort_skipped_frames = 0;  // statistics: list-free frames of a ribbon program that did not sort (enqueue_ribbon_sort)
+    uint32_t sort_path_frames[3] = {0, 0, 0};  // statistics: frames sorted by k_sort_tile1 / k_sort_fill + k_sort_small + k_sort_merge / the eight radix passes (enqueue_ribbon_sort)
     bool tick_sign_seen = false;       // sticky: some frame's AGE tick of some instance was negative, -0 or NaN (stage_program_frame; enqueue_ribbon_sort)
     uint64_t serial = 0;            // identity across destruction (HNB_OPT_JIT_ASYNC: a finished compilation looks its program up by it)
     bool jit_pending = false;
@@ -2206,6 +2207,11 @@ static void enqueue_ribbon_sort(HnbContext* ctx, HnbProgram* p, hipStream_t st) 
     // Keys are age BITS: a uniform tick keeps their order only while no age crosses zero. No tick of this program was ever negative or NaN
     // (HnbProgram::tick_sign_seen, sticky), and an age that carries the sign bit makes the update publish a no-death bound of 0 (update_stream_chunk), so
     // a frame whose lists were skipped follows a frame in which every alive age was +0 or above.
+    // The skip relies on two things nothing in this function can see:
+    //   * every sort path below is STABLE (equal keys keep their list order). Ages that differ in one frame can round to the same float in a later one;
+    //     a sort that ran then would leave such a pair as it stands, and only therefore not sorting leaves the same list;
+    //   * every update kernel publishes a no-death bound of 0 for an age with the sign bit, so a list-free frame never follows ages below +0.
+    // (tests/test_gpu_ribbon_sort.py: stability of each path on long runs of equal keys; the skip on and off over ages that collide under rounding.)
     if (!p->plan.lists && !p->ribbon_hist.dirty && p->frames_run > 0u && !p->tick_sign_seen) { p->sort_skipped_frames += 1; return; }
     if (p->plan.ribbon.rotate) {  // the spawns go in front and k_compact has written the survivors in that order (CompactArgs::rotate_front): nothing to sort
         p->sort_rotated_frames += 1;
@@ -2218,6 +2224,7 @@ static void enqueue_ribbon_sort(HnbContext* ctx, HnbProgram* p, hipStream_t st) 
     const uint32_t tiles = n * so.chunks_per_inst;
     if (so.chunks_per_inst == 1u) {   // the instance is one tile: fill, the range's radix passes and the merge in one launch
         k_sort_tile1<<<n, kBlock, 0, st>>>(so, p->d_inst_base, mo);
+        p->sort_path_frames[0] += 1;
         p->ribbon_hist.dirty = false;
         return;
     }
@@ -2226,7 +2233,9 @@ static void enqueue_ribbon_sort(HnbContext* ctx, HnbProgram* p, hipStream_t st) 
     // are issued (a 40-particle lightning bolt whose ages are not provably ordered took 8 + 8 empty launches per frame)
     if ((proven && p->plan.ribbon.max_spawn <= kSortSmallMax) || p->dev.capacity <= kSortSmallMax / 4u) {
         k_sort_small<<<n, kBlock, 0, st>>>(so, p->d_inst_base, mo);
+        p->sort_path_frames[1] += 1;
     } else {
+        p->sort_path_frames[2] += 1;
         for (uint32_t pass = 0; pass < 8; ++pass) {
             k_sort_hist<<<tiles, kBlock, 0, st>>>(so, p->d_inst_base, mo, pass);
             k_sort_scatter<<<tiles, kBlock, 0, st>>>(so, p->d_inst_base, mo, pass);
@@ -2984,6 +2993,8 @@ int hnb_program_kernel_info(HnbProgram* prog, char* buf, size_t buf_size) {
     if (prog->has_ribbons && prog->ring_frames) s += "\nlist kept as a ring (no row rewritten): " + std::to_string(prog->ring_frames) + " frames";
     if (prog->has_ribbons && prog->sort_skipped_frames) s += "\nribbon sorts skipped in list-free frames: " + std::to_string(prog->sort_skipped_frames) + " frames";
     if (prog->has_ribbons) s += "\nribbon sorts by rotation: " + std::to_string(prog->sort_rotated_frames) + " of " + std::to_string(prog->frames_run) + " frames" + (prog->ribbon_facts.front_static ? "" : " (not eligible)");
+    if (prog->has_ribbons) s += "\nribbon sorts by path: one-tile " + std::to_string(prog->sort_path_frames[0]) + ", one-workgroup " + std::to_string(prog->sort_path_frames[1]) +
+                                ", multi-launch " + std::to_string(prog->sort_path_frames[2]) + " frames";
     if (prog->merged_frames) s += "\nupdate served by a merged launch (small programs of the context share one): " + std::to_string(prog->merged_frames) + " frames";
     if (prog->unmerged_frames) s += "\nkept out of the shared launches (the loaded set module does not know this program; its own specialised kernels): " + std::to_string(prog->unmerged_frames) + " frames";
     if (prog->set_frames) s += "\n... by the context's set module (the program's specialised code behind the shared launch): " + std::to_string(prog->set_frames) + " frames";
