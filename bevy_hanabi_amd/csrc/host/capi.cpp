@@ -309,6 +309,22 @@ int hnb_asset_particle_layout(const HnbAsset* asset, uint32_t* out_attrs, uint32
     });
 }
 
+int hnb_asset_particle_layout_aos(const HnbAsset* asset, HnbExportField* out_fields, uint32_t cap, uint32_t* out_count, uint32_t* out_stride) {
+    REQUIRE(asset && out_count && out_stride, "NULL argument");
+    return guarded([&] {
+        const ParticleLayout layout = asset->a.reference_particle_layout();
+        uint32_t n = 0;
+        for (const AttributeLayout& e : layout.entries()) {
+            if (e.padding) continue;   // (the PAD fields: bytes no field covers, which the export writes as zero)
+            if (n < cap && out_fields) { out_fields[n].attr = (uint16_t)e.attribute.id; out_fields[n].reserved = 0; out_fields[n].dst_offset = e.offset; }
+            n += 1;
+        }
+        *out_count = n;
+        *out_stride = layout.min_binding_size();
+        return HNB_OK;
+    });
+}
+
 int hnb_lower(const HnbAsset* asset, void** out_blob, size_t* out_size) {
     REQUIRE(asset && out_blob && out_size, "NULL argument");
     return guarded([&] { return copy_out(lower(asset->a), out_blob, out_size); });

@@ -30,6 +30,7 @@ ABI_SYMBOLS = [
     "hnb_effect_device_view", "hnb_effect_materialise", "hnb_jit_precompile_set", "hnb_effect_check", "hnb_effect_compare", "hnb_comm_describe", "hnb_program_device_view",
     "hnb_simulate_steps", "hnb_effect_set_frames_ahead", "hnb_program_set_frames_ahead", "hnb_ctx_step_stats",
     "hnb_program_prepare_steps", "hnb_jit_precompile_steps",
+    "hnb_effect_export", "hnb_program_export",
 ]
 
 # hnb_ctx_set_option (include/hanabi_amd.h): name -> option id
@@ -121,6 +122,36 @@ class ProgramView(C.Structure):
                 ("alive_list_off", C.c_uint64 * 2), ("dead_list_off", C.c_uint64), ("attrs", ProgramAttr * 40)]
 
 
+EXPORT_MAX_FIELDS = 16   # HNB_EXPORT_MAX_FIELDS
+
+
+class ExportField(C.Structure):
+    """HnbExportField: attribute `attr` goes to byte `dst_offset` of every record."""
+    _fields_ = [("attr", C.c_uint16), ("reserved", C.c_uint16), ("dst_offset", C.c_uint32)]
+
+
+class ExportDesc(C.Structure):
+    """HnbExportDesc (hnb_effect_export / hnb_program_export): the record layout and the device buffers of a packed export."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_fields", C.c_uint32), ("record_stride", C.c_uint32), ("flags", C.c_uint32),
+                ("dst", C.c_void_p), ("dst_capacity_records", C.c_uint64), ("out_count", C.c_void_p), ("fields", ExportField * EXPORT_MAX_FIELDS)]
+
+
+def export_desc(fields, dst_ptr, stride, capacity_records, count_ptr=None):
+    """fields: (attribute id, byte offset) pairs, or ExportField objects -> ExportDesc. More than EXPORT_MAX_FIELDS fields keep their count:
+    the library refuses them."""
+    d = ExportDesc()
+    d.struct_size = C.sizeof(ExportDesc)
+    fields = list(fields)
+    d.n_fields = len(fields)
+    for i, f in enumerate(fields[:EXPORT_MAX_FIELDS]):
+        d.fields[i] = f if isinstance(f, ExportField) else ExportField(int(f[0]), 0, int(f[1]))
+    d.record_stride = int(stride)
+    d.dst = C.c_void_p(int(dst_ptr))
+    d.dst_capacity_records = int(capacity_records)
+    d.out_count = C.c_void_p(int(count_ptr)) if count_ptr else None
+    return d
+
+
 _lib = None
 
 
@@ -184,6 +215,8 @@ def load_library():
         lib.hnb_ctx_step_stats.argtypes = [C.c_void_p, C.POINTER(StepStats)]
         lib.hnb_program_prepare_steps.argtypes = [C.c_void_p]
         lib.hnb_jit_precompile_steps.argtypes = [C.c_char_p, C.c_size_t]
+        lib.hnb_effect_export.argtypes = [C.c_void_p, C.POINTER(ExportDesc)]
+        lib.hnb_program_export.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.c_void_p]
         _lib = lib
     return _lib
 
@@ -409,6 +442,13 @@ class Program:
         _check(self._lib.hnb_program_device_view(self._h, C.byref(v)))
         return v
 
+    def export(self, fields, dst_ptr, stride, capacity_records, count_ptr=None, offsets_ptr=None):
+        """hnb_program_export: the alive particles of ALL instances, packed back to back in instance order, as records of `stride` bytes at the
+        device address dst_ptr; offsets_ptr (device u32[n_instances + 1]) receives each instance's first record and the total, count_ptr (device
+        u32[2]) the records written and the alive rows found. Raw device addresses; asynchronous on the simulation stream."""
+        d = export_desc(fields, dst_ptr, stride, capacity_records, count_ptr)
+        _check(self._lib.hnb_program_export(self._h, C.byref(d), C.c_void_p(int(offsets_ptr)) if offsets_ptr else None))
+
     def kernel_info(self):
         """Which kernels run this program: 'init=jit|interp|none update=aot-stream:<name>|jit-stream|jit-generic|interp-*'."""
         buf = C.create_string_buffer(4096)
@@ -503,6 +543,13 @@ class Effect:
         for a in attr_ids:
             mask |= 1 << int(a)
         _check(self._lib.hnb_effect_materialise(self._h, mask))
+
+    def export(self, fields, dst_ptr, stride, capacity_records, count_ptr=None):
+        """hnb_effect_export: record r of the buffer at the device address dst_ptr = the particle in row r of the alive list; fields are
+        (attribute id, byte offset) pairs, `stride` the bytes per record, count_ptr (device u32[2], optional) receives the records written and
+        the alive rows found. Raw device addresses; enqueued on the simulation stream behind the frames so far, nothing synchronises."""
+        d = export_desc(fields, dst_ptr, stride, capacity_records, count_ptr)
+        _check(self._lib.hnb_effect_export(self._h, C.byref(d)))
 
     def check(self):
         """hnb_effect_check: list permutation, alive bytes, age < lifetime, fault flag - on the device; a dict with "ok"."""

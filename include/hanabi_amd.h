@@ -538,6 +538,53 @@ int hnb_program_device_view(HnbProgram* prog, HnbProgramView* out_view);
  * returns at once. A no-op for attributes that are never stale. */
 int hnb_effect_materialise(HnbEffect* fx, uint64_t attr_mask);
 
+/* ---- Packed output -------------------------------------------------------------------------------------------------------------
+ * For a consumer that does not want planes indexed by slot plus a list (a renderer with a fixed instance or vertex format, a host of the
+ * reference that wants its interleaved array<Particle> as vfx_render.wgsl reads it, a baking pipeline that wants an [alive, k] tensor): one
+ * kernel that turns them into "row r of the list = record r of your buffer". The caller describes the record: which attribute goes where.
+ * Record contents
+ *   Record r, for r < min(alive_count, dst_capacity_records), holds the attributes of the particle in row r of the alive list - the row of
+ *   the formula above: alive_list[list_column & 1][((list_column >> 1) + r) % capacity]. Each field is ncomp x 4 bytes copied bit for bit to
+ *   dst + r * record_stride + dst_offset. Bytes of a written record that no field covers are written as ZERO: the export owns whole records
+ *   (which is what lets it store full lines). Records at and past the written count are not touched. HNB_ATTR_ID exports slot_base + slot,
+ *   the value the init and update programs see.
+ *   HNB_ERR_INVALID_ARG (with hnb_last_error text; nothing is enqueued) for: HNB_ATTR_PARTICLE_COUNTER, an attribute the program's layout
+ *   lacks, overlapping fields, a field that is not dword aligned or ends past the stride, a stride that is no multiple of 4 or above 256,
+ *   dst NULL or not 16-byte aligned, n_fields == 0 or above HNB_EXPORT_MAX_FIELDS, flags or a field's `reserved` not 0, another struct_size.
+ * Ordering and state
+ *   Asynchronous: enqueued on the context's simulation stream behind every frame enqueued so far, like a frame. No host synchronisation and
+ *   no readback: alive_count, the list column and the head are read from the effect's HnbDeviceMeta row on the device; the grid is sized from
+ *   the capacity and workgroups past the count leave after one scalar load. dst and out_count must stay valid until the stream has run the
+ *   export (the same contract as a consumer kernel behind hnb_effect_device_view). Attributes in stale_attr_mask (AGE under
+ *   HNB_AGE_COHORT_LEAN / ALL and some AUTO programs) are exported as a reader sees them after hnb_effect_materialise: the export enqueues
+ *   that pass itself. Exporting never changes what later frames compute.
+ * Program form
+ *   hnb_program_export packs ALL instances back to back in instance order (hnb_effect_index): out_offsets[k] = first record of instance k,
+ *   out_offsets[n_instances] = the total - an exclusive scan of the rows' alive_count done on the device in front of the gather, which is
+ *   one launch over (tiles, instances). The clamp against dst_capacity_records is global: out_count[0] = min(total, dst_capacity_records),
+ *   out_count[1] = total. Instances that are not simulated (hnb_effect_set_simulated(fx, 0)) export their frozen state. A program without
+ *   instances: HNB_ERR_INVALID_ARG.
+ * The kernels live in a code object of their own that the library carries and loads on the first export of a context; if it cannot be
+ * loaded the call fails with HNB_ERR_HIP - there is no other path. */
+#define HNB_EXPORT_MAX_FIELDS 16u
+typedef struct HnbExportField {
+    uint16_t attr;                   /* HnbAttr */
+    uint16_t reserved;               /* 0 */
+    uint32_t dst_offset;             /* bytes from the record's start; a multiple of 4 */
+} HnbExportField;
+typedef struct HnbExportDesc {
+    uint32_t struct_size;            /* sizeof(HnbExportDesc) of the caller */
+    uint32_t n_fields;               /* 1..HNB_EXPORT_MAX_FIELDS */
+    uint32_t record_stride;          /* bytes per record: a multiple of 4, >= the end of every field, <= 256 */
+    uint32_t flags;                  /* 0 */
+    void* dst;                       /* device pointer, 16-byte aligned */
+    uint64_t dst_capacity_records;
+    uint32_t* out_count;             /* device, may be NULL: [0] = records written, [1] = alive rows found */
+    HnbExportField fields[HNB_EXPORT_MAX_FIELDS];
+} HnbExportDesc;
+int hnb_effect_export(HnbEffect* fx, const HnbExportDesc* desc);
+int hnb_program_export(HnbProgram* prog, const HnbExportDesc* desc, uint32_t* out_offsets /* device [n_instances + 1], may be NULL */);
+
 /* Readback (synchronising; reporting / parity only, never on the frame path). */
 int hnb_effect_metadata(HnbEffect* fx, HnbEffectMetadata* out);
 int hnb_effect_alive_count(HnbEffect* fx, uint32_t* out);

@@ -167,6 +167,12 @@ int hnb_asset_set_prng_seed(HnbAsset* asset, uint32_t seed);
 int hnb_asset_add_modifier(HnbAsset* asset, uint32_t context, const HnbModifierDesc* modifier);
 /* EffectAsset::particle_layout(): attribute ids in ascending order; *out_count receives the total even when it exceeds `cap`. */
 int hnb_asset_particle_layout(const HnbAsset* asset, uint32_t* out_attrs, uint32_t cap, uint32_t* out_count);
+/* The reference's interleaved particle struct for this asset (ParticleLayoutBuilder::build, src/attributes.rs:1516-1670: vec4 first, {vec3 + scalar}
+ * pairs, {vec2 + vec2} pairs, padded vec3, the odd vec2, scalars) as the fields of an HnbExportDesc: one entry per stored attribute with its byte
+ * offset, in struct order (padding fields are left out: the export writes them as zero); *out_stride = the struct's size rounded up to 16, the pitch of
+ * the reference's array<Particle>. With these, hnb_effect_export writes the particle buffer vfx_render.wgsl reads, in list order. *out_count receives
+ * the total even when it exceeds `cap`. */
+int hnb_asset_particle_layout_aos(const HnbAsset* asset, HnbExportField* out_fields, uint32_t cap, uint32_t* out_count, uint32_t* out_stride);
 /* EffectShaderSources::generate counterpart: the HnbProgram blob for hnb_program_create() / hnb_program_validate(). */
 int hnb_lower(const HnbAsset* asset, void** out_blob, size_t* out_size);
 /* The reference's on-disk asset format: RON text as EffectAsset::serialize writes and ::deserialize reads it
