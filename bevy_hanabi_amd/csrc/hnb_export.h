@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/hanabi_amd.h"
+#include "hnb_sort_key.h"
 
 namespace hnb {
 
@@ -27,8 +28,11 @@ struct ExportArgs {
     uint64_t dst_capacity;          // records
     uint64_t alive_off[2];          // bytes from the slab base
     uint64_t pad_mask;              // bit d: dword d of a record is covered by no field (written as zero)
-    uint32_t capacity, stride_dw, n_fields, tile_rows, slot_base, reserved;
+    uint32_t capacity, stride_dw, n_fields, tile_rows, slot_base;
+    uint32_t order_pitch;           // sorted export: slots between the two value buffers below
     ExportFieldArg fields[HNB_EXPORT_MAX_FIELDS];
+    const uint32_t* order;          // sorted export (k_export_sort_rows_*): the value buffers [2][order_pitch] of the sort, row r of the result = record r;
+    const uint32_t* order_state;    //   the sort's ExportSortState words say which of the two holds the result. NULL for k_export_rows_*: the list is read
 };
 
 // The four instantiations of k_export_rows by the LDS image they declare: records of up to 32 / 64 / 128 bytes in tiles of 256 rows, up to 256 bytes in
@@ -36,5 +40,54 @@ struct ExportArgs {
 constexpr uint32_t kExportVariants = 4;
 inline uint32_t export_variant(uint32_t stride_bytes) { return stride_bytes <= 32u ? 0u : stride_bytes <= 64u ? 1u : stride_bytes <= 128u ? 2u : 3u; }
 inline uint32_t export_tile_rows(uint32_t variant) { return variant == 3u ? 128u : 256u; }
+
+
+// ---- sorted export (hnb_effect_export_sorted; kernels: hnb_export_sort.hip, a second code object) ----
+// A least-significant-digit radix sort of (key, slot) pairs, 8 bits per pass, tiles of 4096 rows, digit offsets on two levels (per tile, and per
+// group of 32 tiles) as in hnb_sort.hip.h: no workgroup waits for another.
+constexpr uint32_t kExportSortTile = 4096;     // rows per workgroup
+constexpr uint32_t kExportSortGroup = 32;      // tiles per group of the two-level digit offsets
+constexpr uint32_t kExportSortPasses = 4;      // 32-bit keys
+
+struct ExportSortState {        // zeroed in front of the keys kernel
+    uint32_t or_keys;           // OR of every key
+    uint32_t or_not_keys;       // OR of every complemented key: a bit set in both differs between two keys
+    uint32_t pad[2];
+};
+
+struct ExportSortArgs {
+    const uint64_t* slab;           // [1] the instance's slab base address
+    const HnbDeviceMeta* meta;      // [1] its row after the frames enqueued so far
+    uint32_t* keys;                 // [2][pitch] ping-pong
+    uint32_t* vals;                 // [2][pitch] slots, ping-pong
+    uint32_t* hist;                 // [4 digits][tiles][256]: per-tile digit counts
+    uint32_t* gsum;                 // [2][4 digits][groups][256]: digit counts per group of tiles; set 0 from the keys kernel (rows in list order), set 1 from
+                                    //   k_export_sort_hist (rows as the earlier passes left them); zeroed in front of the keys kernel
+    ExportSortState* state;
+    uint64_t alive_off[2];          // bytes from the slab base
+    uint64_t plane_off;             // the key source: the POSITION plane (DEPTH, DISTANCE) or the scalar attribute's
+    uint32_t capacity, pitch, tiles, groups;
+    uint32_t key;                   // HNB_SORT_KEY_*
+    uint32_t is_f32;                // HNB_SORT_KEY_ATTR: the plane holds f32
+    uint32_t descending;
+    float v[3];
+};
+
+struct ExportSortPass { bool active; uint32_t ran, src; };
+// Pass p (0..3) of the sort: whether it runs at all (its digit differs between two keys), how many passes ran before it, and which ping-pong
+// buffer it reads; p = 4 gives the buffer that holds the result.
+HNB_SORT_KEY_FN ExportSortPass export_sort_pass(uint32_t varying, uint32_t pass) {
+    ExportSortPass r;
+    r.ran = 0;
+    for (uint32_t q = 0; q < pass; ++q) r.ran += ((varying >> (8u * q)) & 0xffu) ? 1u : 0u;
+    r.active = pass < kExportSortPasses && ((varying >> (8u * (pass & 3u))) & 0xffu) != 0u;
+    r.src = r.ran & 1u;
+    return r;
+}
+
+HNB_SORT_KEY_FN const uint32_t* export_order_of(const ExportArgs& a) {
+    const uint32_t varying = a.order_state[0] & a.order_state[1];
+    return a.order + (size_t)export_sort_pass(varying, kExportSortPasses).src * a.order_pitch;
+}
 
 }  // namespace hnb

@@ -10,107 +10,17 @@
 //            the program form an instance's first record is wherever the instances before it end, so up to 3 leading dwords go out singly.
 //            The last, partial tile stores whole records only.
 // k_export_offsets: the program form's exclusive scan of the instances' alive counts (one workgroup), in front of the gather.
+// The body of the gather is export_rows in hnb_export_rows.hip.h, shared with the sorted export's code object (hnb_export_sort.hip).
 #include <hip/hip_runtime.h>
 
-#include "hnb_export.h"
+#include "hnb_export_rows.hip.h"
 
 using namespace hnb;
 
-namespace {
-
-__device__ __forceinline__ uint32_t ring_index(uint32_t head, uint32_t r, uint32_t capacity) {   // head < capacity, r < capacity
-    const uint32_t i = head + r;
-    return (i >= capacity || i < head) ? i - capacity : i;
-}
-
-__device__ __forceinline__ uint4 load_field(const char* __restrict__ base, const ExportFieldArg f, uint32_t slot, uint32_t id) {
-    const uint32_t nc = f.ncomp_flags & 7u;
-    uint4 v = make_uint4(id, 0u, 0u, 0u);
-    if (f.ncomp_flags & kExportIdField) return v;
-    const uint32_t* p = reinterpret_cast<const uint32_t*>(base + f.plane_off) + (size_t)slot * nc;
-    if (nc == 4u) v = *reinterpret_cast<const uint4*>(p);                       // planes are 256-byte aligned: a vec4 slot is 16-byte aligned, a vec2 slot 8
-    else if (nc == 3u) { v.x = p[0]; v.y = p[1]; v.z = p[2]; }
-    else if (nc == 2u) { const uint2 q = *reinterpret_cast<const uint2*>(p); v.x = q.x; v.y = q.y; }
-    else v.x = p[0];
-    return v;
-}
-
-__device__ __forceinline__ void store_field(uint32_t* rec, const ExportFieldArg f, const uint4 v) {
-    const uint32_t nc = f.ncomp_flags & 7u;
-    uint32_t* d = rec + f.dst_dw;
-    d[0] = v.x;
-    if (nc > 1u) d[1] = v.y;
-    if (nc > 2u) d[2] = v.z;
-    if (nc > 3u) d[3] = v.w;
-}
-
-template <uint32_t LDS_DWORDS>
-__device__ __forceinline__ void export_rows(const ExportArgs& a) {
-    __shared__ __attribute__((aligned(16))) uint32_t image[LDS_DWORDS];
-    const uint32_t k = blockIdx.y, tid = threadIdx.x;
-    const HnbDeviceMeta m = a.meta[k];                                           // uniform: scalar loads
-    const uint32_t n = m.alive_count;
-    const uint32_t row0 = blockIdx.x * a.tile_rows;
-    if (a.out_count && blockIdx.x == 0u && tid == 0u) {                           // (effect form only)
-        a.out_count[0] = (uint64_t)n < a.dst_capacity ? n : (uint32_t)a.dst_capacity;
-        a.out_count[1] = n;
-    }
-    if (row0 >= n) return;                                                        // the grid is sized from capacity: workgroups past the count leave here
-    const uint64_t first = (a.offsets ? (uint64_t)a.offsets[k] : 0ull) + row0;   // record of the tile's first row
-    if (first >= a.dst_capacity) return;
-    uint32_t rows = n - row0 < a.tile_rows ? n - row0 : a.tile_rows;
-    if ((uint64_t)rows > a.dst_capacity - first) rows = (uint32_t)(a.dst_capacity - first);
-    const char* base = reinterpret_cast<const char*>(a.slabs[k]);
-    const uint32_t* list = reinterpret_cast<const uint32_t*>(base + a.alive_off[m.list_column & 1u]);
-    const uint32_t head = m.list_column >> 1, sdw = a.stride_dw;
-
-    // ---- phase 1: gather into the LDS image ----
-    if (tid < rows) {
-        const uint32_t slot = list[ring_index(head, row0 + tid, a.capacity)];
-        const uint32_t id = (a.slot_bases ? a.slot_bases[k] : a.slot_base) + slot;
-        uint32_t* rec = image + tid * sdw;
-        for (uint32_t f0 = 0; f0 < a.n_fields; f0 += 4u) {                        // four fields' loads in flight together, then their LDS writes
-            uint4 v[4];
-#pragma unroll
-            for (uint32_t q = 0; q < 4u; ++q)
-                if (f0 + q < a.n_fields) v[q] = load_field(base, a.fields[f0 + q], slot, id);
-#pragma unroll
-            for (uint32_t q = 0; q < 4u; ++q)
-                if (f0 + q < a.n_fields) store_field(rec, a.fields[f0 + q], v[q]);
-        }
-        for (uint64_t pm = a.pad_mask; pm; pm &= pm - 1ull) rec[__builtin_ctzll(pm)] = 0u;
-    }
-    __syncthreads();
-
-    // ---- phase 2: stream the image out ----
-    const uint32_t total = rows * sdw;                                            // dwords
-    const uint64_t g0 = first * sdw;                                              // dword index of the tile in dst
-    uint32_t* out = a.dst + g0;
-    uint32_t lead = (4u - (uint32_t)(g0 & 3ull)) & 3u;                            // dwords in front of the first 16-byte boundary (0 in the effect form)
-    if (lead > total) lead = total;
-    const uint32_t nvec = (total - lead) >> 2;
-    if (lead == 0u) {
-        const uint4* src = reinterpret_cast<const uint4*>(image);
-        uint4* o = reinterpret_cast<uint4*>(out);
-        for (uint32_t i = tid; i < nvec; i += kExportBlock) o[i] = src[i];
-    } else {
-        if (tid < lead) out[tid] = image[tid];
-        uint4* o = reinterpret_cast<uint4*>(out + lead);
-        for (uint32_t i = tid; i < nvec; i += kExportBlock) {
-            const uint32_t* s = image + lead + 4u * i;
-            o[i] = make_uint4(s[0], s[1], s[2], s[3]);
-        }
-    }
-    const uint32_t done = lead + 4u * nvec;                                       // a partial tile's last record may end between two boundaries
-    if (tid < total - done) out[done + tid] = image[done + tid];
-}
-
-}  // namespace
-
-extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) k_export_rows_32(const ExportArgs a) { export_rows<256u * 32u / 4u>(a); }
-extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) k_export_rows_64(const ExportArgs a) { export_rows<256u * 64u / 4u>(a); }
-extern "C" __global__ void __launch_bounds__(256) k_export_rows_128(const ExportArgs a) { export_rows<256u * 128u / 4u>(a); }
-extern "C" __global__ void __launch_bounds__(256) k_export_rows_256(const ExportArgs a) { export_rows<128u * 256u / 4u>(a); }
+extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) k_export_rows_32(const ExportArgs a) { export_rows<256u * 32u / 4u, false>(a); }
+extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) k_export_rows_64(const ExportArgs a) { export_rows<256u * 64u / 4u, false>(a); }
+extern "C" __global__ void __launch_bounds__(256) k_export_rows_128(const ExportArgs a) { export_rows<256u * 128u / 4u, false>(a); }
+extern "C" __global__ void __launch_bounds__(256) k_export_rows_256(const ExportArgs a) { export_rows<128u * 256u / 4u, false>(a); }
 
 // offsets[k] = alive rows of the instances in front of k, offsets[n_inst] = their total; out_count (may be NULL): [0] = records the gather writes
 // (the clamp against dst_capacity is global), [1] = the total. One workgroup of 256 lanes: a block scan per 256 instances, a running carry between them.

@@ -1,0 +1,292 @@
+// Sorted export (hnb_effect_export_sorted, include/hanabi_amd.h "Packed output"; DESIGN.md "Sorted export"): the alive particles of ONE effect as
+// packed records in the order of a 32-bit key computed from their planes - depth along a direction, squared distance from a point, or a scalar
+// attribute. A code object of its own, like hnb_export.hip: nothing here is part of the fat binary of libhanabi_amd.so.
+//
+// The simulation is only read: the alive list, the planes and the metadata row stay as they are, (key, slot) pairs live in scratch the library owns
+// per effect. A stable least-significant-digit radix sort, 8 bits per pass, over tiles of 4096 rows with 256 lanes, the design of hnb_sort.hip.h:
+//   k_export_sort_keys     row r: slot = list[ring(head, r)], key from plane[slot]; writes key[0][r], val[0][r]; in the same pass the tile's 256-bin
+//                          counts of all four digits (LDS) -> hist[d][tile], added into gsum[0][d][tile / 32], and the OR of the keys and of their
+//                          complements. A digit's per-tile counts describe the rows IN LIST ORDER: they serve the first pass that runs, whichever
+//                          digit that is. (The counts of a later pass depend on where the earlier ones put the rows; knowing them in advance is what
+//                          a decoupled look-back buys, and no workgroup here ever waits for another.)
+//   k_export_sort_hist     in front of every later pass: its digit's per-tile counts of the rows as they lie now -> hist[d], gsum[1][d].
+//   k_export_sort_scatter  once per digit: a tile derives its 256 digit offsets itself (digit totals and the groups before its own from gsum, the
+//                          earlier tiles of its group from hist), ranks its keys stably (wave match by ballots, waves in order, rounds in order)
+//                          and moves (key, slot) to the other buffer.
+//   A pass whose digit is the same in every key (OR of keys & OR of complements has no bit in it) returns after two scalar loads, in both kernels;
+//   which buffer a pass reads and which one holds the result follows from the passes that ran (export_sort_pass).
+//   k_export_sort_tile     an effect of at most 4096 slots: keys, every pass and the state words by ONE workgroup in one launch.
+//   k_export_sort_rows_*   the gather of hnb_export_rows.hip.h with slot = order[r].
+// Every loop is bounded by the capacity; every grid is sized from it, and workgroups past alive_count leave after the scalar loads.
+#include <hip/hip_runtime.h>
+
+#include "hnb_export_rows.hip.h"
+
+#pragma clang fp contract(off)   // the key arithmetic is rounded operation by operation (the unit is also built with -ffp-contract=off)
+
+using namespace hnb;
+
+namespace {
+
+constexpr uint32_t kBlock = kExportBlock;
+constexpr uint32_t kWaves = kBlock / 64u;
+constexpr uint32_t kRounds = kExportSortTile / kBlock;
+
+struct SortSource {
+    const uint32_t* list;
+    const uint32_t* plane;
+    uint32_t head, n;
+};
+
+__device__ __forceinline__ SortSource sort_source(const ExportSortArgs& a) {
+    const HnbDeviceMeta m = a.meta[0];                                            // uniform: scalar loads
+    const char* base = reinterpret_cast<const char*>(a.slab[0]);
+    SortSource s;
+    s.list = reinterpret_cast<const uint32_t*>(base + a.alive_off[m.list_column & 1u]);
+    s.plane = reinterpret_cast<const uint32_t*>(base + a.plane_off);
+    s.head = m.list_column >> 1;
+    s.n = m.alive_count < a.capacity ? m.alive_count : a.capacity;
+    return s;
+}
+
+// include/hanabi_amd.h states these formulas; every operation is rounded on its own, in this order.
+__device__ __forceinline__ uint32_t key_of_slot(const ExportSortArgs& a, const uint32_t* __restrict__ plane, uint32_t slot) {
+    if (a.key == HNB_SORT_KEY_ATTR) return sort_key_of(plane[slot], a.is_f32 != 0u, a.descending != 0u);
+    const uint32_t* p = plane + (size_t)slot * 3u;
+    const float x = __uint_as_float(p[0]), y = __uint_as_float(p[1]), z = __uint_as_float(p[2]);
+    float d;
+    if (a.key == HNB_SORT_KEY_DEPTH) {
+        const float xy = x * a.v[0] + y * a.v[1];
+        d = xy + z * a.v[2];
+    } else {
+        const float ex = x - a.v[0], ey = y - a.v[1], ez = z - a.v[2];
+        const float xy = ex * ex + ey * ey;
+        d = xy + ez * ez;
+    }
+    return sort_key_of(__float_as_uint(d), true, a.descending != 0u);
+}
+
+__device__ __forceinline__ uint32_t wave_or(uint32_t v) {
+#pragma unroll
+    for (uint32_t off = 32; off > 0; off >>= 1) v |= (uint32_t)__shfl_xor((int)v, off, 64);
+    return v;
+}
+
+// One round's digits into a 256-bin LDS histogram. Called by whole waves; the valid lanes of a wave are its first ones. A wave whose valid lanes
+// all hold one digit (the upper bytes of most keys; a constant key) adds once instead of queueing 64 atomics on one bank.
+__device__ __forceinline__ void hist_add(uint32_t* h, uint32_t digit, bool valid, uint32_t lane) {
+    const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)digit);
+    if (__ballot(valid && digit != first) == 0ull) {
+        const uint32_t cnt = (uint32_t)__popcll(__ballot(valid));
+        if (lane == 0u && cnt) atomicAdd(&h[first], cnt);
+    } else if (valid) {
+        atomicAdd(&h[digit], 1u);
+    }
+}
+
+// 256 digit totals (thread d holds digit d's) -> their exclusive prefix sum; s_tmp: kWaves words of LDS. Ends behind a barrier.
+__device__ __forceinline__ uint32_t digit_scan(uint32_t total, uint32_t* s_tmp, uint32_t lane, uint32_t wave) {
+    uint32_t incl = total;
+#pragma unroll
+    for (uint32_t off = 1; off < 64; off <<= 1) { const uint32_t y = (uint32_t)__shfl_up((int)incl, off, 64); if (lane >= off) incl += y; }
+    __syncthreads();
+    if (lane == 63u) s_tmp[wave] = incl;
+    __syncthreads();
+    uint32_t base = incl - total;
+    for (uint32_t w = 0; w < wave; ++w) base += s_tmp[w];
+    __syncthreads();
+    return base;
+}
+
+// One round of 256 rows of a scatter pass: stable ranks by wave match, then the move. s_base[d]: where digit d's next row goes; s_cnt: [kWaves][256],
+// zero on entry and on exit. Ends behind a barrier. Every destination is below n: the bases come from counts of these same keys.
+__device__ __forceinline__ void scatter_round(uint32_t key, uint32_t val, bool valid, uint32_t shift, uint32_t* s_base, uint32_t (*s_cnt)[256], uint32_t* dkey, uint32_t* dval,
+                                              uint32_t n, uint32_t tid, uint32_t lane, uint32_t wave) {
+    const uint32_t digit = (key >> shift) & 0xffu;
+    uint64_t same = __ballot(valid);                                              // lanes of this wave holding the same digit (stable: earlier lanes first)
+#pragma unroll
+    for (uint32_t b = 0; b < 8; ++b) {
+        const bool bit = (digit >> b) & 1u;
+        const uint64_t bal = __ballot(bit);
+        same &= bit ? bal : ~bal;
+    }
+    const uint32_t rank = (uint32_t)__popcll(same & ((1ull << lane) - 1ull));
+    if (valid && rank == 0u) s_cnt[wave][digit] = (uint32_t)__popcll(same);
+    __syncthreads();
+    if (valid) {
+        uint32_t off = s_base[digit] + rank;
+        for (uint32_t w = 0; w < wave; ++w) off += s_cnt[w][digit];
+        if (off < n) { dkey[off] = key; dval[off] = val; }
+    }
+    __syncthreads();
+    uint32_t add = 0;                                                             // thread d advances digit d's base past this round and clears the round's counters
+#pragma unroll
+    for (uint32_t w = 0; w < kWaves; ++w) { add += s_cnt[w][tid]; s_cnt[w][tid] = 0u; }
+    s_base[tid] += add;
+    __syncthreads();
+}
+
+}  // namespace
+
+extern "C" __global__ void __launch_bounds__(256) k_export_sort_keys(const ExportSortArgs a) {
+    __shared__ uint32_t s_hist[kExportSortPasses][256];
+    const uint32_t j = blockIdx.x, tid = threadIdx.x, lane = tid & 63u;
+    const SortSource s = sort_source(a);
+    if (j >= a.tiles || j * kExportSortTile >= s.n) return;
+#pragma unroll
+    for (uint32_t d = 0; d < kExportSortPasses; ++d) s_hist[d][tid] = 0u;
+    __syncthreads();
+    uint32_t ork = 0u, ornk = 0u;
+    for (uint32_t r = 0; r < kRounds; ++r) {
+        const uint32_t rbase = j * kExportSortTile + r * kBlock;
+        if (rbase >= s.n) break;
+        const uint32_t i = rbase + tid;
+        const bool valid = i < s.n;
+        uint32_t key = 0u;
+        if (valid) {
+            const uint32_t slot = s.list[ring_index(s.head, i, a.capacity)];
+            key = key_of_slot(a, s.plane, slot);
+            a.keys[i] = key;
+            a.vals[i] = slot;
+            ork |= key; ornk |= ~key;
+        }
+#pragma unroll
+        for (uint32_t d = 0; d < kExportSortPasses; ++d) hist_add(s_hist[d], (key >> (8u * d)) & 0xffu, valid, lane);
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t d = 0; d < kExportSortPasses; ++d) {
+        const uint32_t c = s_hist[d][tid];
+        a.hist[((size_t)d * a.tiles + j) * 256u + tid] = c;
+        if (c) atomicAdd(a.gsum + ((size_t)d * a.groups + j / kExportSortGroup) * 256u + tid, c);
+    }
+    ork = wave_or(ork); ornk = wave_or(ornk);
+    if (lane == 0u) { atomicOr(&a.state->or_keys, ork); atomicOr(&a.state->or_not_keys, ornk); }
+}
+
+extern "C" __global__ void __launch_bounds__(256) k_export_sort_hist(const ExportSortArgs a, uint32_t pass) {
+    __shared__ uint32_t s_hist[256];
+    const ExportSortPass sp = export_sort_pass(a.state->or_keys & a.state->or_not_keys, pass);
+    if (!sp.active || sp.ran == 0u) return;                                       // (the first pass that runs has the keys kernel's counts)
+    const uint32_t j = blockIdx.x, tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t alive = a.meta[0].alive_count;
+    const uint32_t n = alive < a.capacity ? alive : a.capacity;
+    if (j >= a.tiles || j * kExportSortTile >= n) return;
+    s_hist[tid] = 0u;
+    __syncthreads();
+    const uint32_t* skey = a.keys + (size_t)sp.src * a.pitch;
+    for (uint32_t r = 0; r < kRounds; ++r) {
+        const uint32_t rbase = j * kExportSortTile + r * kBlock;
+        if (rbase >= n) break;
+        const uint32_t i = rbase + tid;
+        const bool valid = i < n;
+        const uint32_t key = valid ? skey[i] : 0u;
+        hist_add(s_hist, (key >> (8u * pass)) & 0xffu, valid, lane);
+    }
+    __syncthreads();
+    const uint32_t c = s_hist[tid];
+    a.hist[((size_t)pass * a.tiles + j) * 256u + tid] = c;
+    if (c) atomicAdd(a.gsum + ((size_t)(kExportSortPasses + pass) * a.groups + j / kExportSortGroup) * 256u + tid, c);
+}
+
+extern "C" __global__ void __launch_bounds__(256) k_export_sort_scatter(const ExportSortArgs a, uint32_t pass) {
+    __shared__ uint32_t s_base[256];
+    __shared__ uint32_t s_cnt[kWaves][256];
+    const ExportSortPass sp = export_sort_pass(a.state->or_keys & a.state->or_not_keys, pass);
+    if (!sp.active) return;
+    const uint32_t j = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t alive = a.meta[0].alive_count;
+    const uint32_t n = alive < a.capacity ? alive : a.capacity;
+    if (j >= a.tiles || j * kExportSortTile >= n) return;
+    const uint32_t* skey = a.keys + (size_t)sp.src * a.pitch;
+    const uint32_t* sval = a.vals + (size_t)sp.src * a.pitch;
+    uint32_t* dkey = a.keys + (size_t)(sp.src ^ 1u) * a.pitch;
+    uint32_t* dval = a.vals + (size_t)(sp.src ^ 1u) * a.pitch;
+    {   // offset(d, j) = sum_{d' < d} total(d') + sum_{groups before mine} gsum(g, d) + sum_{earlier tiles of my group} hist(j', d)
+        const uint32_t used_groups = ((n + kExportSortTile - 1u) / kExportSortTile + kExportSortGroup - 1u) / kExportSortGroup;   // groups holding rows; <= a.groups
+        const uint32_t* gs = a.gsum + (size_t)((sp.ran ? kExportSortPasses : 0u) + pass) * a.groups * 256u;
+        const uint32_t* hist = a.hist + (size_t)pass * a.tiles * 256u;
+        const uint32_t my_group = j / kExportSortGroup;
+        uint32_t total = 0, before = 0;
+        for (uint32_t g = 0; g < used_groups; ++g) { const uint32_t v = gs[(size_t)g * 256u + tid]; total += v; if (g < my_group) before += v; }
+        for (uint32_t t = my_group * kExportSortGroup; t < j; ++t) before += hist[(size_t)t * 256u + tid];
+        const uint32_t digit_base = digit_scan(total, s_base, lane, wave);
+        s_base[tid] = digit_base + before;
+    }
+#pragma unroll
+    for (uint32_t w = 0; w < kWaves; ++w) s_cnt[w][tid] = 0u;
+    __syncthreads();
+    for (uint32_t r = 0; r < kRounds; ++r) {
+        const uint32_t rbase = j * kExportSortTile + r * kBlock;
+        if (rbase >= n) break;
+        const uint32_t i = rbase + tid;
+        const bool valid = i < n;
+        scatter_round(valid ? skey[i] : 0u, valid ? sval[i] : 0u, valid, 8u * pass, s_base, s_cnt, dkey, dval, n, tid, lane, wave);
+    }
+}
+
+// An effect of at most kExportSortTile slots: the whole sort by one workgroup in one launch. The passes communicate through the key / value buffers
+// in global memory as they do across launches (a workgroup sees its own stores behind a barrier); the state words are written for the gather.
+extern "C" __global__ void __launch_bounds__(256) k_export_sort_tile(const ExportSortArgs a) {
+    __shared__ uint32_t s_base[256];
+    __shared__ uint32_t s_cnt[kWaves][256];
+    __shared__ uint32_t s_or[2][kWaves];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const SortSource s = sort_source(a);
+    const uint32_t n = s.n < kExportSortTile ? s.n : kExportSortTile;             // (capacity <= kExportSortTile: the host launches this kernel for nothing else)
+    uint32_t ork = 0u, ornk = 0u;
+    for (uint32_t r = 0; r < kRounds; ++r) {
+        const uint32_t i = r * kBlock + tid;
+        if (i >= n) break;
+        const uint32_t slot = s.list[ring_index(s.head, i, a.capacity)];
+        const uint32_t key = key_of_slot(a, s.plane, slot);
+        a.keys[i] = key;
+        a.vals[i] = slot;
+        ork |= key; ornk |= ~key;
+    }
+    ork = wave_or(ork); ornk = wave_or(ornk);
+    if (lane == 0u) { s_or[0][wave] = ork; s_or[1][wave] = ornk; }
+    __syncthreads();
+    ork = 0u; ornk = 0u;
+#pragma unroll
+    for (uint32_t w = 0; w < kWaves; ++w) { ork |= s_or[0][w]; ornk |= s_or[1][w]; }
+    if (tid == 0u) { a.state->or_keys = ork; a.state->or_not_keys = ornk; }
+    const uint32_t varying = ork & ornk;
+    if (n == 0u || varying == 0u) return;
+    uint32_t src = 0u;
+    for (uint32_t pass = 0; pass < kExportSortPasses; ++pass) {
+        if (((varying >> (8u * pass)) & 0xffu) == 0u) continue;
+        const uint32_t* skey = a.keys + (size_t)src * a.pitch;
+        const uint32_t* sval = a.vals + (size_t)src * a.pitch;
+        uint32_t* dkey = a.keys + (size_t)(src ^ 1u) * a.pitch;
+        uint32_t* dval = a.vals + (size_t)(src ^ 1u) * a.pitch;
+        s_base[tid] = 0u;
+#pragma unroll
+        for (uint32_t w = 0; w < kWaves; ++w) s_cnt[w][tid] = 0u;
+        __syncthreads();
+        for (uint32_t r = 0; r < kRounds; ++r) {
+            const uint32_t rbase = r * kBlock;
+            if (rbase >= n) break;
+            const bool valid = rbase + tid < n;
+            hist_add(s_base, ((valid ? skey[rbase + tid] : 0u) >> (8u * pass)) & 0xffu, valid, lane);
+        }
+        __syncthreads();
+        const uint32_t total = s_base[tid];
+        const uint32_t digit_base = digit_scan(total, s_or[0], lane, wave);
+        s_base[tid] = digit_base;
+        __syncthreads();
+        for (uint32_t r = 0; r < kRounds; ++r) {
+            const uint32_t rbase = r * kBlock;
+            if (rbase >= n) break;
+            const uint32_t i = rbase + tid;
+            const bool valid = i < n;
+            scatter_round(valid ? skey[i] : 0u, valid ? sval[i] : 0u, valid, 8u * pass, s_base, s_cnt, dkey, dval, n, tid, lane, wave);
+        }
+        src ^= 1u;   // (== export_sort_pass(varying, pass + 1).src: the gather finds the result where the multi-launch path leaves it)
+    }
+}
+
+extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) k_export_sort_rows_32(const ExportArgs a) { export_rows<256u * 32u / 4u, true>(a); }
+extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) k_export_sort_rows_64(const ExportArgs a) { export_rows<256u * 64u / 4u, true>(a); }
+extern "C" __global__ void __launch_bounds__(256) k_export_sort_rows_128(const ExportArgs a) { export_rows<256u * 128u / 4u, true>(a); }
+extern "C" __global__ void __launch_bounds__(256) k_export_sort_rows_256(const ExportArgs a) { export_rows<128u * 256u / 4u, true>(a); }

@@ -30,7 +30,7 @@ ABI_SYMBOLS = [
     "hnb_effect_device_view", "hnb_effect_materialise", "hnb_jit_precompile_set", "hnb_effect_check", "hnb_effect_compare", "hnb_comm_describe", "hnb_program_device_view",
     "hnb_simulate_steps", "hnb_effect_set_frames_ahead", "hnb_program_set_frames_ahead", "hnb_ctx_step_stats",
     "hnb_program_prepare_steps", "hnb_jit_precompile_steps",
-    "hnb_effect_export", "hnb_program_export",
+    "hnb_effect_export", "hnb_program_export", "hnb_effect_export_sorted",
 ]
 
 # hnb_ctx_set_option (include/hanabi_amd.h): name -> option id
@@ -152,6 +152,26 @@ def export_desc(fields, dst_ptr, stride, capacity_records, count_ptr=None):
     return d
 
 
+SORT_KEY_DEPTH, SORT_KEY_DISTANCE, SORT_KEY_ATTR = 0, 1, 2   # HNB_SORT_KEY_*
+SORT_KEYS = {"depth": SORT_KEY_DEPTH, "distance": SORT_KEY_DISTANCE, "attr": SORT_KEY_ATTR}
+
+
+class ExportSort(C.Structure):
+    """HnbExportSort (hnb_effect_export_sorted): the key the records are ordered by."""
+    _fields_ = [("struct_size", C.c_uint32), ("key", C.c_uint32), ("attr", C.c_uint32), ("descending", C.c_uint32), ("v", C.c_float * 3), ("reserved", C.c_uint32)]
+
+
+def export_sort(key, v=(0, 0, 0), attr=0, descending=False):
+    """key: "depth" | "distance" | "attr" or a HNB_SORT_KEY_* value -> ExportSort."""
+    s = ExportSort()
+    s.struct_size = C.sizeof(ExportSort)
+    s.key = SORT_KEYS[key] if isinstance(key, str) else int(key)
+    s.attr = int(attr)
+    s.descending = int(descending)
+    s.v = (C.c_float * 3)(*[float(x) for x in v])
+    return s
+
+
 _lib = None
 
 
@@ -217,6 +237,7 @@ def load_library():
         lib.hnb_jit_precompile_steps.argtypes = [C.c_char_p, C.c_size_t]
         lib.hnb_effect_export.argtypes = [C.c_void_p, C.POINTER(ExportDesc)]
         lib.hnb_program_export.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.c_void_p]
+        lib.hnb_effect_export_sorted.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.POINTER(ExportSort)]
         _lib = lib
     return _lib
 
@@ -550,6 +571,14 @@ class Effect:
         the alive rows found. Raw device addresses; enqueued on the simulation stream behind the frames so far, nothing synchronises."""
         d = export_desc(fields, dst_ptr, stride, capacity_records, count_ptr)
         _check(self._lib.hnb_effect_export(self._h, C.byref(d)))
+
+    def export_sorted(self, fields, dst_ptr, stride, capacity_records, count_ptr=None, *, key, v=(0, 0, 0), attr=0, descending=False):
+        """hnb_effect_export_sorted: the records of export(), ordered by a 32-bit key per particle - key "depth" (along the direction v), "distance"
+        (squared, from the point v) or "attr" (the scalar attribute `attr`); ties keep list order, ascending and descending alike. A destination of
+        K records receives the first K of that order."""
+        d = export_desc(fields, dst_ptr, stride, capacity_records, count_ptr)
+        s = export_sort(key, v, attr, descending)
+        _check(self._lib.hnb_effect_export_sorted(self._h, C.byref(d), C.byref(s)))
 
     def check(self):
         """hnb_effect_check: list permutation, alive bytes, age < lifetime, fault flag - on the device; a dict with "ok"."""

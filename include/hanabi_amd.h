@@ -585,6 +585,48 @@ typedef struct HnbExportDesc {
 int hnb_effect_export(HnbEffect* fx, const HnbExportDesc* desc);
 int hnb_program_export(HnbProgram* prog, const HnbExportDesc* desc, uint32_t* out_offsets /* device [n_instances + 1], may be NULL */);
 
+/* Sorted export: the records of hnb_effect_export, but in the order of a 32-bit key computed per particle - back to front for a renderer that
+ * alpha-blends, "nearest K" / "oldest K" with a destination of K records. One effect; there is no program form.
+ * Order
+ *   Every alive row gets a 32-bit key k from a value of the particle (below). For an f32 value with bits b:
+ *       k = b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u)
+ *   - the total order -NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN, no special case. For every other scalar type (u32, i32, bool): k = b, the
+ *   order of the bits as an unsigned number. With `descending`, k = ~k. Record r of dst is the particle with the r-th smallest k; rows with EQUAL
+ *   keys keep their list order, ascending and descending alike (the sort is stable: descending is not the reverse of ascending).
+ * Key values (every f32 operation rounded on its own, in the order written; nothing is contracted into a fused multiply-add - a binary32
+ * restatement on the host gives the same bits). p = POSITION as stored:
+ *   HNB_SORT_KEY_DEPTH     d = (p.x*v[0] + p.y*v[1]) + p.z*v[2]                                       distance along a view direction
+ *   HNB_SORT_KEY_DISTANCE  e = p - v per component; d = (e.x*e.x + e.y*e.y) + e.z*e.z                 squared distance from a point
+ *   HNB_SORT_KEY_ATTR      the scalar attribute `attr` as stored: f32 attributes by the f32 rule, the others by their bits
+ * Clamp
+ *   min(alive_count, dst_capacity_records) records are written: the FIRST ones of the sorted order. out_count[0] = the records written,
+ *   out_count[1] = the alive rows found. Records at and past the written count are not touched; padding dwords of written records are zero.
+ * Everything hnb_effect_export promises holds: enqueued on the simulation stream behind the frames enqueued so far, no host synchronisation, no
+ *   readback, counts and list head read from the HnbDeviceMeta row on the device; stale AGE is materialised first, as a record field and as the
+ *   key; ring lists are read through their head. The simulation is only read: the alive list, the planes and every later frame are bit for bit
+ *   what they would be without the call, and a following hnb_effect_export is in list order.
+ * Errors: HNB_ERR_INVALID_ARG (with hnb_last_error text; nothing is enqueued) for everything hnb_effect_export rejects, and for: sort NULL, another
+ *   struct_size, an unknown key, reserved not 0, descending above 1, DEPTH / DISTANCE on a program whose layout lacks POSITION or with a v[i] that
+ *   is not finite, ATTR with an attribute the layout lacks, with one of more than one component, or with HNB_ATTR_ID / HNB_ATTR_PARTICLE_COUNTER
+ *   (which have no plane).
+ * Scratch: owned by the library, per effect: 16 bytes per slot of capacity (two (key, slot) buffers) plus the digit tables (about 5 bytes per
+ *   slot for capacities above 4096). Allocated by the effect's FIRST sorted export - that one call may synchronise the device once for the
+ *   allocation - and freed with the effect. Exports of one effect reuse it in stream order.
+ * The kernels (a stable radix sort of (key, slot) pairs in which no workgroup waits for another, and the gather of hnb_effect_export fed from its
+ *   result) live in a second code object that the library carries and loads on first use; HNB_ERR_HIP if it cannot be loaded. */
+#define HNB_SORT_KEY_DEPTH    0u   /* d = (p.x*v[0] + p.y*v[1]) + p.z*v[2], p = POSITION: distance along a view direction */
+#define HNB_SORT_KEY_DISTANCE 1u   /* e = p - v (per component); d = (e.x*e.x + e.y*e.y) + e.z*e.z: squared distance from a point */
+#define HNB_SORT_KEY_ATTR     2u   /* the scalar attribute `attr` as stored (f32 or u32 by the layout's scalar type) */
+typedef struct HnbExportSort {
+    uint32_t struct_size;   /* sizeof(HnbExportSort) of the caller */
+    uint32_t key;           /* HNB_SORT_KEY_* */
+    uint32_t attr;          /* HNB_SORT_KEY_ATTR: HnbAttr; otherwise 0 */
+    uint32_t descending;    /* 0: smallest key first; 1: largest key first */
+    float    v[3];          /* DEPTH: direction (need not be normalised); DISTANCE: point; ATTR: 0 */
+    uint32_t reserved;      /* 0 */
+} HnbExportSort;
+int hnb_effect_export_sorted(HnbEffect* fx, const HnbExportDesc* desc, const HnbExportSort* sort);
+
 /* Readback (synchronising; reporting / parity only, never on the frame path). */
 int hnb_effect_metadata(HnbEffect* fx, HnbEffectMetadata* out);
 int hnb_effect_alive_count(HnbEffect* fx, uint32_t* out);
