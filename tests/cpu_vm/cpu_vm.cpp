@@ -206,6 +206,14 @@ int cvm_read_attr(CpuVm* v, uint32_t attr, uint32_t* dst) {
         }
     return -1;
 }
+int cvm_write_attr(CpuVm* v, uint32_t attr, const uint32_t* src) {   // the whole plane, as hnb_effect_write_attr
+    for (size_t a = 0; a < v->attrs.size(); ++a)
+        if (v->attrs[a].attr == attr) {
+            memcpy(v->slab.data() + v->adesc[a].plane_off, src, (size_t)v->h.capacity * v->attrs[a].ncomp * 4);
+            return (int)v->attrs[a].ncomp;
+        }
+    return -1;
+}
 void cvm_read_alive_list(CpuVm* v, uint32_t* dst) { memcpy(dst, v->list[v->write_index].data(), (size_t)v->alive * 4); }
 void cvm_read_dead_list(CpuVm* v, uint32_t* dst) { memcpy(dst, v->dead.data() + v->alive, (size_t)(v->h.capacity - v->alive) * 4); }
 void cvm_read_ublock(CpuVm* v, uint32_t* dst) { memcpy(dst, v->ublock.data(), (size_t)v->h.n_uregs * 4); }

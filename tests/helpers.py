@@ -69,6 +69,7 @@ def _cvm_lib():
         lib.cvm_step.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int]
         lib.cvm_counters.argtypes = [C.c_void_p, C.c_void_p]
         lib.cvm_read_attr.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        lib.cvm_write_attr.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         lib.cvm_read_alive_list.argtypes = [C.c_void_p, C.c_void_p]
         lib.cvm_read_dead_list.argtypes = [C.c_void_p, C.c_void_p]
         _cvm = lib
@@ -119,6 +120,11 @@ class CpuVmRunner:
             assert self.lib.cvm_read_attr(self.h, a.id, buf.ctypes.data) == a.value_type.count
             attrs[a.name] = buf
         return {"counters": counters, "alive": alive, "dead": dead, "attrs": attrs}
+
+    def write_attr(self, attr_id, array):
+        a = np.ascontiguousarray(array)
+        n = self.lib.cvm_write_attr(self.h, int(attr_id), a.ctypes.data)
+        assert n > 0 and a.nbytes == self.capacity * n * 4, (attr_id, n, a.nbytes)
 
     def __del__(self):
         try:
@@ -293,3 +299,127 @@ def math_probe_asset(capacity):
     for m in mods_update:
         asset.update(m)
     return asset
+
+
+# ---- probes of the other operators (tests/math_lattice.py: operands and reference; tests/test_math_lattice.py, tests/test_gpu_math_lattice.py) --------
+def _probe_asset(capacity, w, updates, inits=()):
+    mods_init = [bh.SetAttributeModifier(A.POSITION, w.lit((0.0, 0.0, 0.0)).expr())] + [bh.SetAttributeModifier(attr, e.expr()) for attr, e in inits]
+    mods_update = [bh.SetAttributeModifier(attr, e.expr()) for attr, e in updates]
+    asset = bh.EffectAsset(capacity, bh.SpawnerSettings.once(float(capacity)), w.finish())
+    for m in mods_init:
+        asset.init(m)
+    for m in mods_update:
+        asset.update(m)
+    return asset
+
+
+def _vec4(x, y, z, w_):
+    return x.vec3(y, z).vec4_xyz_w(w_)
+
+
+def ieee_probe_asset(capacity):
+    """(a, b) = F32X2_0, x = F32_0:
+         F32X4_0 = (a + b, a - b, a * b, a / b)      F32X4_1 = (a % b, min(a, b), max(a, b), step(a, b))
+         F32X4_2 = (floor, ceil, round, fract)(x)    F32X4_3 = (sign x, saturate x, abs x, 0)"""
+    w = bh.ExprWriter()
+    p, x = w.attr(A.F32X2_0), w.attr(A.F32_0)
+    a, b = p.x(), p.y()
+    return _probe_asset(capacity, w, [(A.F32X4_0, _vec4(a + b, a - b, a * b, a / b)), (A.F32X4_1, _vec4(a % b, a.min(b), a.max(b), b.step(a))),
+                                      (A.F32X4_2, _vec4(x.floor(), x.ceil(), x.round(), x.fract())), (A.F32X4_3, _vec4(x.sign(), x.saturate(), x.abs(), w.lit(0.0)))])
+
+
+def ternary_probe_asset(capacity):
+    """(a, b, c) = F32X3_0: F32X3_1 = (clamp(a, b, c), mix(a, b, c), smoothstep(a, b, c))"""
+    w = bh.ExprWriter()
+    v = w.attr(A.F32X3_0)
+    a, b, c = v.x(), v.y(), v.z()
+    return _probe_asset(capacity, w, [(A.F32X3_1, a.clamp(b, c).vec3(a.mix(b, c), c.smoothstep(a, b)))])
+
+
+def convert_probe_asset(capacity):
+    """x = F32_0: U32_0 = u32(i32(x)) (the i32's bits), U32_1 = u32(x);  n = U32_2: F32_1 = f32(n), F32_2 = f32(i32(n))"""
+    w = bh.ExprWriter()
+    I, U, F = bh.ValueType(bh.ScalarType.Int), bh.ValueType(bh.ScalarType.Uint), bh.ValueType(bh.ScalarType.Float)
+    x, n = w.attr(A.F32_0), w.attr(A.U32_2)
+    return _probe_asset(capacity, w, [(A.U32_0, x.cast(I).cast(U)), (A.U32_1, x.cast(U)), (A.F32_1, n.cast(F)), (A.F32_2, n.cast(I).cast(F))])
+
+
+# integer operators, three per asset (the integer attributes a program can store: U32_3, COLOR, SPRITE_INDEX); operands a, b, c = U32_0, U32_1, U32_2
+INT_PROBES = {"i32_div": (True, ("div", "rem", "abs")), "i32_min": (True, ("min", "max", "clamp")), "i32_sign": (True, ("sign", "cmp", "mul")),
+              "u32_div": (False, ("div", "rem", "min")), "u32_max": (False, ("max", "clamp", "cmp"))}
+INT_PROBE_OUTPUTS = (A.U32_3, A.COLOR, A.SPRITE_INDEX)
+
+
+def int_probe_asset(capacity, which):
+    """INT_PROBES[which] = (signed, three operators) of (a, b, c) = (U32_0, U32_1, U32_2), as i32 (through a cast, which keeps the bits) or u32, stored to
+    U32_3, COLOR and SPRITE_INDEX. "cmp" is (a < b) + 2 (a <= b) + 4 (a > b) + 8 (a >= b)."""
+    signed, ops = INT_PROBES[which]
+    w = bh.ExprWriter()
+    I, U, F = bh.ValueType(bh.ScalarType.Int), bh.ValueType(bh.ScalarType.Uint), bh.ValueType(bh.ScalarType.Float)
+    T = I if signed else U
+    a, b, c = (w.attr(x).cast(T) if signed else w.attr(x) for x in (A.U32_0, A.U32_1, A.U32_2))
+    k = lambda v: w.lit(bh.Value.i32(v) if signed else bh.Value.u32(v))
+    flag = lambda e: e.cast(F).cast(T)
+
+    def build(op):
+        if op == "cmp":
+            return flag(a.lt(b)) + flag(a.le(b)) * k(2) + flag(a.gt(b)) * k(4) + flag(a.ge(b)) * k(8)
+        return {"div": lambda: a / b, "rem": lambda: a % b, "mul": lambda: a * b, "abs": lambda: a.abs(), "sign": lambda: a.sign(), "min": lambda: a.min(b),
+                "max": lambda: a.max(b), "clamp": lambda: a.clamp(b, c)}[op]()
+    outs = []
+    for attr, op in zip(INT_PROBE_OUTPUTS, ops):
+        e = build(op)
+        outs.append((attr, e.cast(I) if attr == A.SPRITE_INDEX and not signed else (e.cast(U) if attr != A.SPRITE_INDEX and signed else e)))
+    return _probe_asset(capacity, w, outs)
+
+
+def pack_probe_asset(capacity):
+    """v = F32X4_0: U32_0 = pack4x8unorm(v), U32_1 = pack4x8snorm(v);  n = U32_2: F32X4_1 = unpack4x8unorm(n), F32X4_2 = unpack4x8snorm(n)"""
+    w = bh.ExprWriter()
+    v, n = w.attr(A.F32X4_0), w.attr(A.U32_2)
+    return _probe_asset(capacity, w, [(A.U32_0, v.pack4x8unorm()), (A.U32_1, v.pack4x8snorm()), (A.F32X4_1, n.unpack4x8unorm()), (A.F32X4_2, n.unpack4x8snorm())])
+
+
+def vector_probe_asset(capacity):
+    """a = F32X3_0, b = F32X3_1: F32X4_0 = (dot(a, b), length(a), distance(a, b), 0), F32X3_2 = normalize(a), F32X3_3 = cross(a, b)"""
+    w = bh.ExprWriter()
+    a, b = w.attr(A.F32X3_0), w.attr(A.F32X3_1)
+    return _probe_asset(capacity, w, [(A.F32X4_0, _vec4(a.dot(b), a.length(), a.distance(b), w.lit(0.0))), (A.F32X3_2, a.normalized()), (A.F32X3_3, a.cross(b))])
+
+
+def uniform_probe_asset(capacity):
+    """The same operators with every operand an effect property (a, b): lowering hoists such an expression into the uniform stream, which the HOST
+    evaluates once per frame (hnb_math.h compiled into the runtime library). The INIT stores the results, so that the particle spawned in frame i
+    keeps the values of frame i's properties:
+         F32X4_0 = (a + b, a - b, a * b, a / b)      F32X4_1 = (a % b, min, max, step(a, b))      F32X4_2 = (sin, cos, tan, atan)(a)
+         F32X4_3 = (asin, acos, exp, exp2)(a)        F32X3_0 = (log, log2, sqrt)(a)               F32X3_1 = (inverseSqrt a, atan2(a, b), floor a)
+         F32X3_2 = (ceil, round, fract)(a)           F32X3_3 = (sign a, saturate a, clamp(a, b, 1)) F32X2_0 = (mix(a, b, b), smoothstep(a, b, 0.5))"""
+    w = bh.ExprWriter()
+    a, b = w.prop(w.add_property("a", 0.0)), w.prop(w.add_property("b", 0.0))
+    one, half = w.lit(1.0), w.lit(0.5)
+    inits = [(A.F32X4_0, _vec4(a + b, a - b, a * b, a / b)), (A.F32X4_1, _vec4(a % b, a.min(b), a.max(b), b.step(a))),
+             (A.F32X4_2, _vec4(a.sin(), a.cos(), a.tan(), a.atan())), (A.F32X4_3, _vec4(a.asin(), a.acos(), a.exp(), a.exp2())),
+             (A.F32X3_0, a.log().vec3(a.log2(), a.sqrt())), (A.F32X3_1, a.inverse_sqrt().vec3(a.atan2(b), a.floor())),
+             (A.F32X3_2, a.ceil().vec3(a.round(), a.fract())), (A.F32X3_3, a.sign().vec3(a.saturate(), a.clamp(b, one))),
+             (A.F32X2_0, a.mix(b, b).vec2(half.smoothstep(a, b)))]
+    return _probe_asset(capacity, w, [], inits)
+
+
+def program_mnemonics(blob):
+    """{"uniform" | "init" | "update": [mnemonic of every instruction]} of a lowered program (bh.disassemble)"""
+    out, section = {}, None
+    for line in bh.disassemble(blob).split("\n"):
+        if line.rstrip() in ("uniform:", "init:", "update:"):
+            section = line.strip()[:-1]
+            out[section] = []
+        elif section and line.startswith("  "):
+            out[section].append(line.split()[0])
+    return out
+
+
+def lattice_probe_assets(capacity):
+    """every per-particle probe of tests/test_math_lattice.py (tools/warm_jit_cache.py compiles their kernels ahead of the tests)"""
+    import functools
+    fns = [math_probe_asset, ieee_probe_asset, ternary_probe_asset, convert_probe_asset, pack_probe_asset, vector_probe_asset]
+    fns += [functools.partial(int_probe_asset, which=k) for k in INT_PROBES]
+    return [f(capacity) for f in fns] + [uniform_probe_asset(capacity)]

@@ -81,6 +81,13 @@ def test_special_values():
     assert m1(10, 4.0) == 2.0 and m1(11, 4.0) == 0.5
     assert m2(0, 2.0, 10.0) == 1024.0 and m2(0, 8.0, 1.0 / 3.0) == 2.0 and m2(0, 0.0, 0.5) == 0.0 and m2(0, 5.0, 0.0) == 1.0
     assert m2(1, 0.0, 1.0) == 0.0 and m2(1, 1.0, 0.0) == float(np.float32(math.pi / 2)) and m2(1, 0.0, -1.0) == float(np.float32(math.pi))
+    # where the definition is not libm's (hnb_math.h "departs from the host's libm"; the whole table: tests/math_lattice.py PINNED)
+    sign = lambda v: math.copysign(1.0, v)
+    assert math.isnan(m2(0, 1.0, math.inf)) and math.isnan(m2(0, 1.0, -math.inf)) and m2(0, 1.0, 1e38) == 1.0 and m2(0, 1.0, -1e38) == 1.0
+    assert m1(0, -0.0) == 0.0 and sign(m1(0, -0.0)) == 1.0 and m1(2, -0.0) == 0.0 and sign(m1(2, -0.0)) == 1.0      # sin(-0) = tan(-0) = +0 ...
+    assert sign(m1(7, -0.0)) == -1.0 and sign(m1(6, -0.0)) == -1.0                                                    # ... asin and atan keep the sign
+    assert all(math.isnan(m2(1, y, x)) for y in (math.inf, -math.inf) for x in (math.inf, -math.inf))               # atan2(+-inf, +-inf): y / x first
+    assert m2(0, -0.0, -1.0) == math.inf and m2(0, 0.0, -2.0) == math.inf and math.isnan(m2(0, math.nan, 0.0)) and math.isnan(m2(0, -2.0, 2.0))
     # WGSL `%` on floats is truncated remainder: sign follows the dividend
     assert m2(2, 5.5, 2.0) == 1.5 and m2(2, -5.5, 2.0) == -1.5 and m2(2, 5.5, -2.0) == 1.5
 

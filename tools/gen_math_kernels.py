@@ -43,6 +43,16 @@ BIG = '''// ---- transcendental builtins ---------------------------------------
 // The one binary64 piece left: sin / cos / tan of |x| > 65536, where a three-term binary32 Cody-Waite reduction runs out of bits.
 // Such arguments take a (divergent, rarely entered) branch to the round-3 kernel: x - k pi/2 in binary64, minimax polynomials,
 // one rounding to binary32; |x| > 2^40 is defined as x = 0 (sin 0, cos 1), NaN / inf -> NaN.
+//
+// Where this definition departs from the host's libm at special operands (WGSL leaves each of them open; pinned by
+// tests/math_lattice.py PINNED and tests/test_math.py::test_special_values):
+//   sin(-0) = tan(-0) = +0     sin r = fma(r z, S(z), r) adds the product (-0)(S < 0) = +0 to r = -0; asin and atan keep the sign of
+//                              a zero argument (a select on the way out of sin would sit in the hottest init path)
+//   atan2(+-inf, +-inf) = NaN  atan2(y, x) divides first: atan(y / x) with inf / inf = NaN
+//   pow(x < 0, y) = NaN        for every y but 0 (no integer-exponent case); pow(-0, y) is pow(+0, y)
+//   pow(+-0, y < 0) = +inf     also for -0 and an odd y, where libm gives -inf
+//   pow(NaN, 0) = NaN          a NaN operand wins over y == 0; pow(x, 0) = 1 for every other x
+//   pow(1, +-inf) = NaN        exp2(y * log2 x) with inf * 0 = NaN (libm: 1); pow(1, y) = 1 for every finite y
 HNB_HD double d_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
 // Round to nearest integer (ties to even) with two IEEE additions; valid |x| < 2^51. *low32: that integer modulo 2^32 (the low
 // mantissa bits of the biased sum), without a float -> int conversion.
@@ -247,14 +257,16 @@ HNB_HD float f_pow(float x, float y) {{
     if (x == f_inf()) return (y > 0.0f) ? f_inf() : 0.0f;
     float tl;
     const float hi = f_log2_parts(x, &tl);
-    float ph = y * hi;
+    const float p0 = y * hi;                               // NaN only as inf * 0: x == 1 with an infinite y
+    float ph = p0;
     const float pl = f_fma(y, hi, -ph) + y * tl;
     const bool sat = !(f_abs(ph) < 200.0f);                // infinite / huge: the result saturates whatever the low bits are
     if (sat) ph = ph > 0.0f ? 200.0f : -200.0f;
     uint32_t ki;
     const float k = f_rint_bits(ph, &ki);
     const float r = (ph - k) + (sat ? 0.0f : pl);
-    return f_scale2(f_exp2_poly(r), (int32_t)ki);
+    const float v = f_scale2(f_exp2_poly(r), (int32_t)ki);
+    return p0 != p0 ? p0 : v;                              // (the saturation above would have swallowed the NaN)
 }}
 // asin / acos; |x| > 1 -> NaN. |x| <= 1/2: t = asin x directly; beyond: t = asin sqrt((1 - |x|) / 2) ((1 - |x|) / 2 is exact) and
 // asin |x| = pi/2 - 2 t. One polynomial evaluation either way (selects, no branch: a wave has lanes on both sides).

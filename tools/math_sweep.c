@@ -1,11 +1,13 @@
 /* Development tool (hanabi-math v3): every transcendental builtin of oracle/oracle_math.h (== bevy_hanabi_amd/csrc/hnb_math.h in that
  * section) over ALL binary32 arguments against the host's binary64 libm rounded to binary32; pow and atan2 on 4e8 pseudo-random pairs.
  *     gcc -O2 -fopenmp -ffp-contract=off -mfma -Ioracle tools/math_sweep.c -o /tmp/math_sweep -lm && /tmp/math_sweep > profiles/r04_math_sweep.txt
- * (-mfma only makes fmaf an instruction; the library call gives the same bits). About five minutes on 8 cores. */
+ * (-mfma only makes fmaf an instruction; the library call gives the same bits). About five minutes on 8 cores.
+ *     /tmp/math_sweep pow      only the pow line (profiles/math_sweep_pow.txt) */
 #include <math.h>
 #include <omp.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 #include "oracle_math.h"
 
 static long ulp(float a, float b) {
@@ -45,7 +47,8 @@ static void sweep(const char* name, f1 f, d1 ref, float lo, float hi) {
     fflush(stdout);
 }
 static uint64_t mix(uint64_t i) { uint64_t h = i * 0x9E3779B97F4A7C15ull; h ^= h >> 29; h *= 0xBF58476D1CE4E5B9ull; h ^= h >> 32; return h; }
-int main(void) {
+int main(int argc, char** argv) {
+    if (argc > 1 && strcmp(argv[1], "pow") == 0) goto pow_leg;   /* only the pow line */
     sweep("sin", f_sin, sin, -65536.f, 65536.f);
     sweep("cos", f_cos, cos, -65536.f, 65536.f);
     sweep("tan", f_tan, tan, -65536.f, 65536.f);
@@ -58,7 +61,9 @@ int main(void) {
     sweep("asin", f_asin, asin, -INFINITY, INFINITY);
     sweep("acos", f_acos, acos, -INFINITY, INFINITY);
     sweep("atan", f_atan, atan, -INFINITY, INFINITY);
-    long worst = 0, worst32 = 0, sat_bad = 0;
+    long worst, worst32, sat_bad;
+pow_leg:
+    worst = 0; worst32 = 0; sat_bad = 0;
 #pragma omp parallel for reduction(max : worst, worst32) reduction(+ : sat_bad)
     for (long i = 0; i < 400000000L; ++i) {
         const uint64_t h = mix((uint64_t)i);
@@ -75,6 +80,7 @@ int main(void) {
         if (fabs((double)y * log2((double)x)) <= 32.0 && d > worst32) worst32 = d;
     }
     printf("pow    4e8 pseudo-random (x, y): max %ld ulp; max %ld ulp where |y log2 x| <= 32; saturation mismatches %ld\n", worst, worst32, sat_bad);
+    if (argc > 1 && strcmp(argv[1], "pow") == 0) return 0;
     worst = 0;
 #pragma omp parallel for reduction(max : worst)
     for (long i = 0; i < 400000000L; ++i) {

@@ -22,8 +22,8 @@ def main():
     try:
         from test_lowering_cpu import ZOO
         assets += [ZOO[k]() for k in sorted(ZOO)]
-        from helpers import math_probe_asset
-        assets.append(math_probe_asset(4096))
+        from helpers import lattice_probe_assets
+        assets += lattice_probe_assets(4096)   # (math_probe_asset among them)
     except Exception as e:  # tests not present: product programs only
         print("warm_jit_cache: zoo skipped:", e)
     # entries are keyed by the generated source and the kernel headers: drop what older builds left behind
