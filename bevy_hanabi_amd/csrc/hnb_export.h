@@ -33,6 +33,8 @@ struct ExportArgs {
     ExportFieldArg fields[HNB_EXPORT_MAX_FIELDS];
     const uint32_t* order;          // sorted export (k_export_sort_rows_*): the value buffers [2][order_pitch] of the sort, row r of the result = record r;
     const uint32_t* order_state;    //   the sort's ExportSortState words say which of the two holds the result. NULL for k_export_rows_*: the list is read
+    uint32_t n_inst, slot_bits;     // sorted program export, program scope (k_export_sort_rows_all_*): order[r] = export_sort_pack(instance, slot, slot_bits)
+    uint32_t total_cap;             //   ... and n_inst * capacity, the bound of the concatenated row space
 };
 
 // The four instantiations of k_export_rows by the LDS image they declare: records of up to 32 / 64 / 128 bytes in tiles of 256 rows, up to 256 bytes in
@@ -42,7 +44,7 @@ inline uint32_t export_variant(uint32_t stride_bytes) { return stride_bytes <= 3
 inline uint32_t export_tile_rows(uint32_t variant) { return variant == 3u ? 128u : 256u; }
 
 
-// ---- sorted export (hnb_effect_export_sorted; kernels: hnb_export_sort.hip, a second code object) ----
+// ---- sorted export (hnb_effect_export_sorted, hnb_program_export_sorted; kernels: hnb_export_sort.hip, a second code object) ----
 // A least-significant-digit radix sort of (key, slot) pairs, 8 bits per pass, tiles of 4096 rows, digit offsets on two levels (per tile, and per
 // group of 32 tiles) as in hnb_sort.hip.h: no workgroup waits for another.
 constexpr uint32_t kExportSortTile = 4096;     // rows per workgroup
@@ -71,6 +73,12 @@ struct ExportSortArgs {
     uint32_t is_f32;                // HNB_SORT_KEY_ATTR: the plane holds f32
     uint32_t descending;
     float v[3];
+    // sorted program export (hnb_program_export_sorted). Instance scope: keys, vals, hist, gsum and state hold one section per instance, instance k's
+    // at k times the size the members above describe; slab and meta are the program's tables. Program scope: one row space of all instances, pitch /
+    // tiles / groups are those of n_inst * capacity rows.
+    uint32_t n_inst, slot_bits;     // program scope: vals hold export_sort_pack(instance, slot, slot_bits)
+    const uint32_t* offsets;        // program scope: [n_inst + 1] first row of every instance in the concatenated space (k_export_offsets), [n_inst] = rows in all
+    uint32_t total_cap;             // program scope: n_inst * capacity
 };
 
 struct ExportSortPass { bool active; uint32_t ran, src; };
@@ -85,9 +93,29 @@ HNB_SORT_KEY_FN ExportSortPass export_sort_pass(uint32_t varying, uint32_t pass)
     return r;
 }
 
+// Program scope of the sorted program export: one 32-bit value names (instance, slot). slot_bits = ceil(log2(capacity)); the instance sits above
+// them, so the values are ordered like the pairs. A program fits when n_inst << slot_bits <= 2^32.
+HNB_SORT_KEY_FN uint32_t export_sort_slot_bits(uint32_t capacity) {
+    uint32_t b = 0;
+    while (b < 32u && (1ull << b) < (uint64_t)capacity) ++b;
+    return b;
+}
+HNB_SORT_KEY_FN bool export_sort_pack_fits(uint64_t n_inst, uint32_t capacity) {
+    const uint32_t b = export_sort_slot_bits(capacity);
+    return n_inst <= (1ull << (32u - b));
+}
+HNB_SORT_KEY_FN uint32_t export_sort_pack(uint32_t instance, uint32_t slot, uint32_t slot_bits) { return slot_bits >= 32u ? slot : (instance << slot_bits) | slot; }
+HNB_SORT_KEY_FN uint32_t export_sort_unpack_instance(uint32_t v, uint32_t slot_bits) { return slot_bits >= 32u ? 0u : v >> slot_bits; }
+HNB_SORT_KEY_FN uint32_t export_sort_unpack_slot(uint32_t v, uint32_t slot_bits) { return slot_bits >= 32u ? v : v & ((1u << slot_bits) - 1u); }
+
 HNB_SORT_KEY_FN const uint32_t* export_order_of(const ExportArgs& a) {
     const uint32_t varying = a.order_state[0] & a.order_state[1];
     return a.order + (size_t)export_sort_pass(varying, kExportSortPasses).src * a.order_pitch;
+}
+// ... of instance k in the instance scope of the sorted program export: its section of the value buffers, by its own state words
+HNB_SORT_KEY_FN const uint32_t* export_order_of_instance(const ExportArgs& a, uint32_t k) {
+    const uint32_t* st = a.order_state + (size_t)k * (sizeof(ExportSortState) / 4u);
+    return a.order + ((size_t)k * 2u + export_sort_pass(st[0] & st[1], kExportSortPasses).src) * a.order_pitch;
 }
 
 }  // namespace hnb

@@ -1,5 +1,6 @@
 // The gather of the packed export (hnb_export.hip: k_export_rows_*, slots from the alive list; hnb_export_sort.hip: k_export_sort_rows_*, slots
-// from the order a sorted export produced). One body, two instantiations, one per code object.
+// from the order a sorted export produced; k_export_sort_rows_inst_* / _all_*: the two scopes of the sorted program export). One body; the
+// instantiations by where a row's slot comes from.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -33,33 +34,52 @@ __device__ __forceinline__ void store_field(uint32_t* rec, const ExportFieldArg 
     if (nc > 3u) d[3] = v.w;
 }
 
-// ORDERED: row r's slot is order[r] (a sorted export's result; see export_order_of) instead of the list's row r.
-template <uint32_t LDS_DWORDS, bool ORDERED>
+// ORDER: where row r's slot comes from.
+//   kRowsList (false)      the alive list's row r
+//   kRowsOrdered (true)    order[r], a sorted export's result (export_order_of)
+//   kRowsOrderedInstance   instance blockIdx.y's section of the sorted program export's value buffers (export_order_of_instance)
+//   kRowsOrderedProgram    one order over all instances: order[r] names (instance, slot); the rows are those of the concatenated space, the
+//                          instance's slab and slot base are taken per lane
+constexpr uint32_t kRowsList = 0, kRowsOrdered = 1, kRowsOrderedInstance = 2, kRowsOrderedProgram = 3;
+template <uint32_t LDS_DWORDS, uint32_t ORDER>
 __device__ __forceinline__ void export_rows(const ExportArgs& a) {
     __shared__ __attribute__((aligned(16))) uint32_t image[LDS_DWORDS];
-    const uint32_t k = blockIdx.y, tid = threadIdx.x;
+    const uint32_t k = ORDER == kRowsOrderedProgram ? 0u : blockIdx.y, tid = threadIdx.x;
     const HnbDeviceMeta m = a.meta[k];                                           // uniform: scalar loads
-    const uint32_t n = m.alive_count;
+    uint32_t n = m.alive_count;
+    if constexpr (ORDER == kRowsOrderedProgram) {                                 // every instance's rows; the sort bounded them the same way
+        const uint32_t all = a.offsets[a.n_inst];
+        n = all < a.total_cap ? all : a.total_cap;
+    }
     const uint32_t row0 = blockIdx.x * a.tile_rows;
     if (a.out_count && blockIdx.x == 0u && tid == 0u) {                           // (effect form only)
         a.out_count[0] = (uint64_t)n < a.dst_capacity ? n : (uint32_t)a.dst_capacity;
         a.out_count[1] = n;
     }
     if (row0 >= n) return;                                                        // the grid is sized from capacity: workgroups past the count leave here
-    const uint64_t first = (a.offsets ? (uint64_t)a.offsets[k] : 0ull) + row0;   // record of the tile's first row
+    const uint64_t first = (ORDER != kRowsOrderedProgram && a.offsets ? (uint64_t)a.offsets[k] : 0ull) + row0;   // record of the tile's first row
     if (first >= a.dst_capacity) return;
     uint32_t rows = n - row0 < a.tile_rows ? n - row0 : a.tile_rows;
     if ((uint64_t)rows > a.dst_capacity - first) rows = (uint32_t)(a.dst_capacity - first);
-    const char* base = reinterpret_cast<const char*>(a.slabs[k]);
-    const uint32_t* list = reinterpret_cast<const uint32_t*>(base + a.alive_off[m.list_column & 1u]);
+    const char* base0 = reinterpret_cast<const char*>(a.slabs[k]);
+    const uint32_t* list = reinterpret_cast<const uint32_t*>(base0 + a.alive_off[m.list_column & 1u]);
     const uint32_t head = m.list_column >> 1, sdw = a.stride_dw;
 
     // ---- phase 1: gather into the LDS image ----
     if (tid < rows) {
-        uint32_t slot;
-        if constexpr (ORDERED) slot = export_order_of(a)[row0 + tid];
-        else slot = list[ring_index(head, row0 + tid, a.capacity)];
-        const uint32_t id = (a.slot_bases ? a.slot_bases[k] : a.slot_base) + slot;
+        uint32_t slot, ki = k;
+        const char* base = base0;
+        if constexpr (ORDER == kRowsOrdered) slot = export_order_of(a)[row0 + tid];
+        else if constexpr (ORDER == kRowsOrderedInstance) slot = export_order_of_instance(a, k)[row0 + tid];
+        else if constexpr (ORDER == kRowsOrderedProgram) {
+            const uint32_t v = export_order_of(a)[row0 + tid];
+            ki = export_sort_unpack_instance(v, a.slot_bits);
+            slot = export_sort_unpack_slot(v, a.slot_bits);
+            if (ki >= a.n_inst) ki = a.n_inst - 1u;                               // (the sort packed only pairs inside the program; nothing is read outside it whatever the buffer holds)
+            if (slot >= a.capacity) slot = a.capacity - 1u;
+            base = reinterpret_cast<const char*>(a.slabs[ki]);
+        } else slot = list[ring_index(head, row0 + tid, a.capacity)];
+        const uint32_t id = (a.slot_bases ? a.slot_bases[ki] : a.slot_base) + slot;
         uint32_t* rec = image + tid * sdw;
         for (uint32_t f0 = 0; f0 < a.n_fields; f0 += 4u) {                        // four fields' loads in flight together, then their LDS writes
             uint4 v[4];

@@ -17,6 +17,10 @@
 //   which buffer a pass reads and which one holds the result follows from the passes that ran (export_sort_pass).
 //   k_export_sort_tile     an effect of at most 4096 slots: keys, every pass and the state words by ONE workgroup in one launch.
 //   k_export_sort_rows_*   the gather of hnb_export_rows.hip.h with slot = order[r].
+// hnb_program_export_sorted (DESIGN.md "Sorted export, program form") runs the same bodies for every instance of a program:
+//   k_export_sort_*_inst   instance scope: instance = blockIdx.y, in its own section of every buffer, by its own meta row and state words.
+//   k_export_sort_fill, _hist_all, _scatter_all   program scope: all instances' rows as one space, values name (instance, slot).
+//   k_export_sort_rows_inst_* / _all_*   their gathers.
 // Every loop is bounded by the capacity; every grid is sized from it, and workgroups past alive_count leave after the scalar loads.
 #include <hip/hip_runtime.h>
 
@@ -32,15 +36,54 @@ constexpr uint32_t kBlock = kExportBlock;
 constexpr uint32_t kWaves = kBlock / 64u;
 constexpr uint32_t kRounds = kExportSortTile / kBlock;
 
+// Which rows a sort kernel works on. kSortEffect: one effect (hnb_effect_export_sorted), everything as ExportSortArgs describes it. kSortBatch: the
+// instance scope of hnb_program_export_sorted, instance blockIdx.y in its own section of every buffer, by its own meta row and state words.
+// kSortGlobal: the program scope, the rows of all instances as one space of offsets[n_inst] rows.
+constexpr uint32_t kSortEffect = 0, kSortBatch = 1, kSortGlobal = 2;
+
+struct SortView {
+    uint32_t* keys;
+    uint32_t* vals;
+    uint32_t* hist;
+    uint32_t* gsum;
+    ExportSortState* state;
+};
+
+template <uint32_t MODE>
+__device__ __forceinline__ SortView sort_view(const ExportSortArgs& a) {
+    SortView v = {a.keys, a.vals, a.hist, a.gsum, a.state};
+    if constexpr (MODE == kSortBatch) {
+        const size_t k = blockIdx.y;
+        v.keys += k * 2u * a.pitch;
+        v.vals += k * 2u * a.pitch;
+        v.hist += k * kExportSortPasses * a.tiles * 256u;
+        v.gsum += k * 2u * kExportSortPasses * a.groups * 256u;
+        v.state += k;
+    }
+    return v;
+}
+
+// rows to sort: uniform (scalar loads)
+template <uint32_t MODE>
+__device__ __forceinline__ uint32_t sort_rows(const ExportSortArgs& a) {
+    if constexpr (MODE == kSortGlobal) {
+        const uint32_t all = a.offsets[a.n_inst];
+        return all < a.total_cap ? all : a.total_cap;
+    } else {
+        const uint32_t alive = a.meta[MODE == kSortBatch ? blockIdx.y : 0u].alive_count;
+        return alive < a.capacity ? alive : a.capacity;
+    }
+}
+
 struct SortSource {
     const uint32_t* list;
     const uint32_t* plane;
     uint32_t head, n;
 };
 
-__device__ __forceinline__ SortSource sort_source(const ExportSortArgs& a) {
-    const HnbDeviceMeta m = a.meta[0];                                            // uniform: scalar loads
-    const char* base = reinterpret_cast<const char*>(a.slab[0]);
+__device__ __forceinline__ SortSource sort_source(const ExportSortArgs& a, uint32_t k = 0u) {
+    const HnbDeviceMeta m = a.meta[k];                                            // uniform: scalar loads
+    const char* base = reinterpret_cast<const char*>(a.slab[k]);
     SortSource s;
     s.list = reinterpret_cast<const uint32_t*>(base + a.alive_off[m.list_column & 1u]);
     s.plane = reinterpret_cast<const uint32_t*>(base + a.plane_off);
@@ -128,10 +171,14 @@ __device__ __forceinline__ void scatter_round(uint32_t key, uint32_t val, bool v
 
 }  // namespace
 
-extern "C" __global__ void __launch_bounds__(256) k_export_sort_keys(const ExportSortArgs a) {
+namespace {
+
+template <uint32_t MODE>
+__device__ __forceinline__ void sort_keys_body(const ExportSortArgs& a) {
     __shared__ uint32_t s_hist[kExportSortPasses][256];
     const uint32_t j = blockIdx.x, tid = threadIdx.x, lane = tid & 63u;
-    const SortSource s = sort_source(a);
+    const SortSource s = sort_source(a, MODE == kSortBatch ? blockIdx.y : 0u);
+    const SortView v = sort_view<MODE>(a);
     if (j >= a.tiles || j * kExportSortTile >= s.n) return;
 #pragma unroll
     for (uint32_t d = 0; d < kExportSortPasses; ++d) s_hist[d][tid] = 0u;
@@ -146,8 +193,8 @@ extern "C" __global__ void __launch_bounds__(256) k_export_sort_keys(const Expor
         if (valid) {
             const uint32_t slot = s.list[ring_index(s.head, i, a.capacity)];
             key = key_of_slot(a, s.plane, slot);
-            a.keys[i] = key;
-            a.vals[i] = slot;
+            v.keys[i] = key;
+            v.vals[i] = slot;
             ork |= key; ornk |= ~key;
         }
 #pragma unroll
@@ -157,24 +204,26 @@ extern "C" __global__ void __launch_bounds__(256) k_export_sort_keys(const Expor
 #pragma unroll
     for (uint32_t d = 0; d < kExportSortPasses; ++d) {
         const uint32_t c = s_hist[d][tid];
-        a.hist[((size_t)d * a.tiles + j) * 256u + tid] = c;
-        if (c) atomicAdd(a.gsum + ((size_t)d * a.groups + j / kExportSortGroup) * 256u + tid, c);
+        v.hist[((size_t)d * a.tiles + j) * 256u + tid] = c;
+        if (c) atomicAdd(v.gsum + ((size_t)d * a.groups + j / kExportSortGroup) * 256u + tid, c);
     }
     ork = wave_or(ork); ornk = wave_or(ornk);
-    if (lane == 0u) { atomicOr(&a.state->or_keys, ork); atomicOr(&a.state->or_not_keys, ornk); }
+    if (lane == 0u) { atomicOr(&v.state->or_keys, ork); atomicOr(&v.state->or_not_keys, ornk); }
 }
 
-extern "C" __global__ void __launch_bounds__(256) k_export_sort_hist(const ExportSortArgs a, uint32_t pass) {
+// kSortGlobal: in front of EVERY pass that runs, the first included (the fill kernel's tiles are not the passes': it leaves no counts), into set 1.
+template <uint32_t MODE>
+__device__ __forceinline__ void sort_hist_body(const ExportSortArgs& a, uint32_t pass) {
     __shared__ uint32_t s_hist[256];
-    const ExportSortPass sp = export_sort_pass(a.state->or_keys & a.state->or_not_keys, pass);
-    if (!sp.active || sp.ran == 0u) return;                                       // (the first pass that runs has the keys kernel's counts)
+    const SortView v = sort_view<MODE>(a);
+    const ExportSortPass sp = export_sort_pass(v.state->or_keys & v.state->or_not_keys, pass);
+    if (!sp.active || (MODE != kSortGlobal && sp.ran == 0u)) return;              // (the first pass that runs has the keys kernel's counts)
     const uint32_t j = blockIdx.x, tid = threadIdx.x, lane = tid & 63u;
-    const uint32_t alive = a.meta[0].alive_count;
-    const uint32_t n = alive < a.capacity ? alive : a.capacity;
+    const uint32_t n = sort_rows<MODE>(a);
     if (j >= a.tiles || j * kExportSortTile >= n) return;
     s_hist[tid] = 0u;
     __syncthreads();
-    const uint32_t* skey = a.keys + (size_t)sp.src * a.pitch;
+    const uint32_t* skey = v.keys + (size_t)sp.src * a.pitch;
     for (uint32_t r = 0; r < kRounds; ++r) {
         const uint32_t rbase = j * kExportSortTile + r * kBlock;
         if (rbase >= n) break;
@@ -185,30 +234,31 @@ extern "C" __global__ void __launch_bounds__(256) k_export_sort_hist(const Expor
     }
     __syncthreads();
     const uint32_t c = s_hist[tid];
-    a.hist[((size_t)pass * a.tiles + j) * 256u + tid] = c;
-    if (c) atomicAdd(a.gsum + ((size_t)(kExportSortPasses + pass) * a.groups + j / kExportSortGroup) * 256u + tid, c);
+    v.hist[((size_t)pass * a.tiles + j) * 256u + tid] = c;
+    if (c) atomicAdd(v.gsum + ((size_t)(kExportSortPasses + pass) * a.groups + j / kExportSortGroup) * 256u + tid, c);
 }
 
-extern "C" __global__ void __launch_bounds__(256) k_export_sort_scatter(const ExportSortArgs a, uint32_t pass) {
+template <uint32_t MODE>
+__device__ __forceinline__ void sort_scatter_body(const ExportSortArgs& a, uint32_t pass) {
     __shared__ uint32_t s_base[256];
     __shared__ uint32_t s_cnt[kWaves][256];
-    const ExportSortPass sp = export_sort_pass(a.state->or_keys & a.state->or_not_keys, pass);
+    const SortView v = sort_view<MODE>(a);
+    const ExportSortPass sp = export_sort_pass(v.state->or_keys & v.state->or_not_keys, pass);
     if (!sp.active) return;
     const uint32_t j = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t alive = a.meta[0].alive_count;
-    const uint32_t n = alive < a.capacity ? alive : a.capacity;
+    const uint32_t n = sort_rows<MODE>(a);
     if (j >= a.tiles || j * kExportSortTile >= n) return;
-    const uint32_t* skey = a.keys + (size_t)sp.src * a.pitch;
-    const uint32_t* sval = a.vals + (size_t)sp.src * a.pitch;
-    uint32_t* dkey = a.keys + (size_t)(sp.src ^ 1u) * a.pitch;
-    uint32_t* dval = a.vals + (size_t)(sp.src ^ 1u) * a.pitch;
+    const uint32_t* skey = v.keys + (size_t)sp.src * a.pitch;
+    const uint32_t* sval = v.vals + (size_t)sp.src * a.pitch;
+    uint32_t* dkey = v.keys + (size_t)(sp.src ^ 1u) * a.pitch;
+    uint32_t* dval = v.vals + (size_t)(sp.src ^ 1u) * a.pitch;
     {   // offset(d, j) = sum_{d' < d} total(d') + sum_{groups before mine} gsum(g, d) + sum_{earlier tiles of my group} hist(j', d)
         const uint32_t used_groups = ((n + kExportSortTile - 1u) / kExportSortTile + kExportSortGroup - 1u) / kExportSortGroup;   // groups holding rows; <= a.groups
-        const uint32_t* gs = a.gsum + (size_t)((sp.ran ? kExportSortPasses : 0u) + pass) * a.groups * 256u;
-        const uint32_t* hist = a.hist + (size_t)pass * a.tiles * 256u;
+        const uint32_t* gs = v.gsum + (size_t)((MODE == kSortGlobal || sp.ran ? kExportSortPasses : 0u) + pass) * a.groups * 256u;
+        const uint32_t* hist = v.hist + (size_t)pass * a.tiles * 256u;
         const uint32_t my_group = j / kExportSortGroup;
         uint32_t total = 0, before = 0;
-        for (uint32_t g = 0; g < used_groups; ++g) { const uint32_t v = gs[(size_t)g * 256u + tid]; total += v; if (g < my_group) before += v; }
+        for (uint32_t g = 0; g < used_groups; ++g) { const uint32_t c = gs[(size_t)g * 256u + tid]; total += c; if (g < my_group) before += c; }
         for (uint32_t t = my_group * kExportSortGroup; t < j; ++t) before += hist[(size_t)t * 256u + tid];
         const uint32_t digit_base = digit_scan(total, s_base, lane, wave);
         s_base[tid] = digit_base + before;
@@ -225,14 +275,16 @@ extern "C" __global__ void __launch_bounds__(256) k_export_sort_scatter(const Ex
     }
 }
 
-// An effect of at most kExportSortTile slots: the whole sort by one workgroup in one launch. The passes communicate through the key / value buffers
-// in global memory as they do across launches (a workgroup sees its own stores behind a barrier); the state words are written for the gather.
-extern "C" __global__ void __launch_bounds__(256) k_export_sort_tile(const ExportSortArgs a) {
+// Instances of at most kExportSortTile slots: the whole sort of one by one workgroup in one launch. The passes communicate through the key / value
+// buffers in global memory as they do across launches (a workgroup sees its own stores behind a barrier); the state words are written for the gather.
+template <uint32_t MODE>
+__device__ __forceinline__ void sort_tile_body(const ExportSortArgs& a) {
     __shared__ uint32_t s_base[256];
     __shared__ uint32_t s_cnt[kWaves][256];
     __shared__ uint32_t s_or[2][kWaves];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const SortSource s = sort_source(a);
+    const SortSource s = sort_source(a, MODE == kSortBatch ? blockIdx.y : 0u);
+    const SortView v = sort_view<MODE>(a);
     const uint32_t n = s.n < kExportSortTile ? s.n : kExportSortTile;             // (capacity <= kExportSortTile: the host launches this kernel for nothing else)
     uint32_t ork = 0u, ornk = 0u;
     for (uint32_t r = 0; r < kRounds; ++r) {
@@ -240,8 +292,8 @@ extern "C" __global__ void __launch_bounds__(256) k_export_sort_tile(const Expor
         if (i >= n) break;
         const uint32_t slot = s.list[ring_index(s.head, i, a.capacity)];
         const uint32_t key = key_of_slot(a, s.plane, slot);
-        a.keys[i] = key;
-        a.vals[i] = slot;
+        v.keys[i] = key;
+        v.vals[i] = slot;
         ork |= key; ornk |= ~key;
     }
     ork = wave_or(ork); ornk = wave_or(ornk);
@@ -250,16 +302,16 @@ extern "C" __global__ void __launch_bounds__(256) k_export_sort_tile(const Expor
     ork = 0u; ornk = 0u;
 #pragma unroll
     for (uint32_t w = 0; w < kWaves; ++w) { ork |= s_or[0][w]; ornk |= s_or[1][w]; }
-    if (tid == 0u) { a.state->or_keys = ork; a.state->or_not_keys = ornk; }
+    if (tid == 0u) { v.state->or_keys = ork; v.state->or_not_keys = ornk; }
     const uint32_t varying = ork & ornk;
     if (n == 0u || varying == 0u) return;
     uint32_t src = 0u;
     for (uint32_t pass = 0; pass < kExportSortPasses; ++pass) {
         if (((varying >> (8u * pass)) & 0xffu) == 0u) continue;
-        const uint32_t* skey = a.keys + (size_t)src * a.pitch;
-        const uint32_t* sval = a.vals + (size_t)src * a.pitch;
-        uint32_t* dkey = a.keys + (size_t)(src ^ 1u) * a.pitch;
-        uint32_t* dval = a.vals + (size_t)(src ^ 1u) * a.pitch;
+        const uint32_t* skey = v.keys + (size_t)src * a.pitch;
+        const uint32_t* sval = v.vals + (size_t)src * a.pitch;
+        uint32_t* dkey = v.keys + (size_t)(src ^ 1u) * a.pitch;
+        uint32_t* dval = v.vals + (size_t)(src ^ 1u) * a.pitch;
         s_base[tid] = 0u;
 #pragma unroll
         for (uint32_t w = 0; w < kWaves; ++w) s_cnt[w][tid] = 0u;
@@ -286,7 +338,60 @@ extern "C" __global__ void __launch_bounds__(256) k_export_sort_tile(const Expor
     }
 }
 
+}  // namespace
+
+extern "C" __global__ void __launch_bounds__(256) k_export_sort_keys(const ExportSortArgs a) { sort_keys_body<kSortEffect>(a); }
+extern "C" __global__ void __launch_bounds__(256) k_export_sort_hist(const ExportSortArgs a, uint32_t pass) { sort_hist_body<kSortEffect>(a, pass); }
+extern "C" __global__ void __launch_bounds__(256) k_export_sort_scatter(const ExportSortArgs a, uint32_t pass) { sort_scatter_body<kSortEffect>(a, pass); }
+extern "C" __global__ void __launch_bounds__(256) k_export_sort_tile(const ExportSortArgs a) { sort_tile_body<kSortEffect>(a); }
+
+// ---- hnb_program_export_sorted, instance scope: the kernels above over (tiles, instances) ----
+extern "C" __global__ void __launch_bounds__(256) k_export_sort_keys_inst(const ExportSortArgs a) { sort_keys_body<kSortBatch>(a); }
+extern "C" __global__ void __launch_bounds__(256) k_export_sort_hist_inst(const ExportSortArgs a, uint32_t pass) { sort_hist_body<kSortBatch>(a, pass); }
+extern "C" __global__ void __launch_bounds__(256) k_export_sort_scatter_inst(const ExportSortArgs a, uint32_t pass) { sort_scatter_body<kSortBatch>(a, pass); }
+extern "C" __global__ void __launch_bounds__(256) k_export_sort_tile_inst(const ExportSortArgs a) { sort_tile_body<kSortBatch>(a); }
+
+// ---- hnb_program_export_sorted, program scope: one row space of offsets[n_inst] rows ----
+// Grid (tiles of an instance, instances): row r of instance k -> position offsets[k] + r of buffer 0, the value names (k, slot); the OR words. An
+// instance's rows start wherever the instances before it end, not on a tile of the passes: no digit counts are left, k_export_sort_hist_all runs
+// in front of every pass.
+extern "C" __global__ void __launch_bounds__(256) k_export_sort_fill(const ExportSortArgs a) {
+    const uint32_t j = blockIdx.x, k = blockIdx.y, tid = threadIdx.x, lane = tid & 63u;
+    if (k >= a.n_inst) return;
+    const SortSource s = sort_source(a, k);
+    if (j * kExportSortTile >= s.n) return;
+    const uint32_t first = a.offsets[k];
+    uint32_t ork = 0u, ornk = 0u;
+    for (uint32_t r = 0; r < kRounds; ++r) {
+        const uint32_t rbase = j * kExportSortTile + r * kBlock;
+        if (rbase >= s.n) break;
+        const uint32_t i = rbase + tid;
+        const uint64_t at = (uint64_t)first + i;
+        if (i < s.n && at < (uint64_t)a.total_cap) {                              // (offsets are sums of counts <= capacity: always inside; the buffers hold total_cap rows)
+            const uint32_t slot = s.list[ring_index(s.head, i, a.capacity)];
+            const uint32_t key = key_of_slot(a, s.plane, slot);
+            a.keys[at] = key;
+            a.vals[at] = export_sort_pack(k, slot, a.slot_bits);
+            ork |= key; ornk |= ~key;
+        }
+    }
+    ork = wave_or(ork); ornk = wave_or(ornk);
+    if (lane == 0u && (ork | ornk)) { atomicOr(&a.state->or_keys, ork); atomicOr(&a.state->or_not_keys, ornk); }
+}
+extern "C" __global__ void __launch_bounds__(256) k_export_sort_hist_all(const ExportSortArgs a, uint32_t pass) { sort_hist_body<kSortGlobal>(a, pass); }
+extern "C" __global__ void __launch_bounds__(256) k_export_sort_scatter_all(const ExportSortArgs a, uint32_t pass) { sort_scatter_body<kSortGlobal>(a, pass); }
+
 extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) k_export_sort_rows_32(const ExportArgs a) { export_rows<256u * 32u / 4u, true>(a); }
 extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) k_export_sort_rows_64(const ExportArgs a) { export_rows<256u * 64u / 4u, true>(a); }
 extern "C" __global__ void __launch_bounds__(256) k_export_sort_rows_128(const ExportArgs a) { export_rows<256u * 128u / 4u, true>(a); }
 extern "C" __global__ void __launch_bounds__(256) k_export_sort_rows_256(const ExportArgs a) { export_rows<128u * 256u / 4u, true>(a); }
+
+extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) k_export_sort_rows_inst_32(const ExportArgs a) { export_rows<256u * 32u / 4u, kRowsOrderedInstance>(a); }
+extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) k_export_sort_rows_inst_64(const ExportArgs a) { export_rows<256u * 64u / 4u, kRowsOrderedInstance>(a); }
+extern "C" __global__ void __launch_bounds__(256) k_export_sort_rows_inst_128(const ExportArgs a) { export_rows<256u * 128u / 4u, kRowsOrderedInstance>(a); }
+extern "C" __global__ void __launch_bounds__(256) k_export_sort_rows_inst_256(const ExportArgs a) { export_rows<128u * 256u / 4u, kRowsOrderedInstance>(a); }
+// (a slab base per lane on top of the four fields in flight: the 64-register budget of the _32 / _64 gathers above would spill)
+extern "C" __global__ void __launch_bounds__(256) k_export_sort_rows_all_32(const ExportArgs a) { export_rows<256u * 32u / 4u, kRowsOrderedProgram>(a); }
+extern "C" __global__ void __launch_bounds__(256) k_export_sort_rows_all_64(const ExportArgs a) { export_rows<256u * 64u / 4u, kRowsOrderedProgram>(a); }
+extern "C" __global__ void __launch_bounds__(256) k_export_sort_rows_all_128(const ExportArgs a) { export_rows<256u * 128u / 4u, kRowsOrderedProgram>(a); }
+extern "C" __global__ void __launch_bounds__(256) k_export_sort_rows_all_256(const ExportArgs a) { export_rows<128u * 256u / 4u, kRowsOrderedProgram>(a); }

@@ -30,7 +30,7 @@ ABI_SYMBOLS = [
     "hnb_effect_device_view", "hnb_effect_materialise", "hnb_jit_precompile_set", "hnb_effect_check", "hnb_effect_compare", "hnb_comm_describe", "hnb_program_device_view",
     "hnb_simulate_steps", "hnb_effect_set_frames_ahead", "hnb_program_set_frames_ahead", "hnb_ctx_step_stats",
     "hnb_program_prepare_steps", "hnb_jit_precompile_steps",
-    "hnb_effect_export", "hnb_program_export", "hnb_effect_export_sorted",
+    "hnb_effect_export", "hnb_program_export", "hnb_effect_export_sorted", "hnb_program_export_sorted",
 ]
 
 # hnb_ctx_set_option (include/hanabi_amd.h): name -> option id
@@ -153,6 +153,8 @@ def export_desc(fields, dst_ptr, stride, capacity_records, count_ptr=None):
 
 
 SORT_KEY_DEPTH, SORT_KEY_DISTANCE, SORT_KEY_ATTR = 0, 1, 2   # HNB_SORT_KEY_*
+SORT_SCOPE_INSTANCE, SORT_SCOPE_PROGRAM = 0, 1              # HNB_SORT_SCOPE_*
+SORT_SCOPES = {"instance": SORT_SCOPE_INSTANCE, "program": SORT_SCOPE_PROGRAM}
 SORT_KEYS = {"depth": SORT_KEY_DEPTH, "distance": SORT_KEY_DISTANCE, "attr": SORT_KEY_ATTR}
 
 
@@ -238,6 +240,7 @@ def load_library():
         lib.hnb_effect_export.argtypes = [C.c_void_p, C.POINTER(ExportDesc)]
         lib.hnb_program_export.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.c_void_p]
         lib.hnb_effect_export_sorted.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.POINTER(ExportSort)]
+        lib.hnb_program_export_sorted.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.POINTER(ExportSort), C.c_uint32, C.c_void_p]
         _lib = lib
     return _lib
 
@@ -469,6 +472,15 @@ class Program:
         u32[2]) the records written and the alive rows found. Raw device addresses; asynchronous on the simulation stream."""
         d = export_desc(fields, dst_ptr, stride, capacity_records, count_ptr)
         _check(self._lib.hnb_program_export(self._h, C.byref(d), C.c_void_p(int(offsets_ptr)) if offsets_ptr else None))
+
+    def export_sorted(self, fields, dst_ptr, stride, capacity_records, count_ptr=None, offsets_ptr=None, *, scope="instance", key, v=(0, 0, 0), attr=0, descending=False):
+        """hnb_program_export_sorted: the records of export(), ordered by a 32-bit key per particle (Effect.export_sorted's keys). scope "instance":
+        the layout of export(), every instance's segment in its own sorted order; scope "program": one order over the particles of all instances
+        (offsets_ptr must be None). Asynchronous."""
+        d = export_desc(fields, dst_ptr, stride, capacity_records, count_ptr)
+        s = export_sort(key, v, attr, descending)
+        sc = SORT_SCOPES[scope] if isinstance(scope, str) else int(scope)
+        _check(self._lib.hnb_program_export_sorted(self._h, C.byref(d), C.byref(s), sc, C.c_void_p(int(offsets_ptr)) if offsets_ptr else None))
 
     def kernel_info(self):
         """Which kernels run this program: 'init=jit|interp|none update=aot-stream:<name>|jit-stream|jit-generic|interp-*'."""

@@ -586,7 +586,8 @@ int hnb_effect_export(HnbEffect* fx, const HnbExportDesc* desc);
 int hnb_program_export(HnbProgram* prog, const HnbExportDesc* desc, uint32_t* out_offsets /* device [n_instances + 1], may be NULL */);
 
 /* Sorted export: the records of hnb_effect_export, but in the order of a 32-bit key computed per particle - back to front for a renderer that
- * alpha-blends, "nearest K" / "oldest K" with a destination of K records. One effect; there is no program form.
+ * alpha-blends, "nearest K" / "oldest K" with a destination of K records. hnb_effect_export_sorted: one effect; hnb_program_export_sorted
+ * (below): every instance of a program in one call.
  * Order
  *   Every alive row gets a 32-bit key k from a value of the particle (below). For an f32 value with bits b:
  *       k = b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u)
@@ -626,6 +627,40 @@ typedef struct HnbExportSort {
     uint32_t reserved;      /* 0 */
 } HnbExportSort;
 int hnb_effect_export_sorted(HnbEffect* fx, const HnbExportDesc* desc, const HnbExportSort* sort);
+
+/* Sorted export, program form: the sorted records of ALL instances of a program - a batch behind one draw - in one call. HnbExportDesc, HnbExportSort,
+ * the keys, their formulas, the f32 key transform and `descending` are those of hnb_effect_export_sorted. `scope` says what is ordered:
+ * HNB_SORT_SCOPE_INSTANCE
+ *   The layout of hnb_program_export: instance k's records occupy [out_offsets[k], out_offsets[k + 1]) in instance order (hnb_effect_index);
+ *   out_offsets is the exclusive scan of the alive counts, out_offsets[n_instances] the total. Inside its segment every instance is in the order
+ *   hnb_effect_export_sorted would give it, ties in list order. The clamp is global, as in hnb_program_export: the first
+ *   min(total, dst_capacity_records) records of that concatenation are written; an instance that is cut keeps the FIRST records of its order.
+ * HNB_SORT_SCOPE_PROGRAM
+ *   ONE order over the alive particles of all instances: record r is the particle with the r-th smallest key of the whole program. Equal keys are
+ *   ordered by instance index, then list row: the sort is stable over the concatenation of the instances' lists, ascending and descending alike.
+ *   A destination of K records receives the first K of that order. out_offsets must be NULL (HNB_ERR_INVALID_ARG otherwise): a consumer tells
+ *   instances apart by an HNB_ATTR_ID field (slot_base + slot, from the instances' slot bases). DEPTH and DISTANCE read POSITION AS STORED: no
+ *   instance transform is applied, so across instances the key is meaningful for global-space effects, or take HNB_SORT_KEY_ATTR.
+ *   The sort names a particle by one 32-bit value, the instance above ceil(log2(capacity)) bits of slot: a program with
+ *   n_instances << ceil(log2(capacity)) > 2^32 is refused in this scope (HNB_ERR_INVALID_ARG).
+ * Both scopes
+ *   out_count[0] = the records written, out_count[1] = the total. Enqueued on the simulation stream behind the frames enqueued so far; no host
+ *   synchronisation and no readback on the steady path: counts, list columns and ring heads are read from the HnbDeviceMeta rows on the device,
+ *   grids are sized from capacities. Stale AGE is materialised for all instances first, as a record field and as the key. Instances that are not
+ *   simulated export their frozen state. The simulation is only read: lists, planes and every later frame are bit for bit what they would be
+ *   without the call, and a following hnb_program_export is in list order.
+ * Errors: HNB_ERR_INVALID_ARG (with hnb_last_error text; nothing is enqueued) for everything hnb_program_export and hnb_effect_export_sorted reject
+ *   (a program without instances or with more than 65535 among them), for `scope` above 1, and for the two refusals of the program scope above.
+ * Scratch: owned by the library, per program: 16 bytes per slot over all instances (two (key, value) buffers) plus the digit tables (about 5 bytes
+ *   per slot for capacities above 4096) and 16 bytes of state per instance. Allocated by the program's FIRST sorted export, and again when the
+ *   program has gained instances since, behind one synchronisation of the stream; freed with the program. The per-effect scratch of
+ *   hnb_effect_export_sorted is another allocation and is not touched.
+ * The kernels are further entries of the second code object: the effect form's sort with the instance as a grid dimension, the same sort over
+ *   the rows of all instances as one space, and the gathers that read the two. */
+#define HNB_SORT_SCOPE_INSTANCE 0u
+#define HNB_SORT_SCOPE_PROGRAM  1u
+int hnb_program_export_sorted(HnbProgram* prog, const HnbExportDesc* desc, const HnbExportSort* sort,
+                              uint32_t scope, uint32_t* out_offsets /* device [n_instances + 1], may be NULL */);
 
 /* Readback (synchronising; reporting / parity only, never on the frame path). */
 int hnb_effect_metadata(HnbEffect* fx, HnbEffectMetadata* out);
