@@ -1564,6 +1564,8 @@ __device__ __forceinline__ void update_stream_chunk(const SlotArgs& args, const 
                 PROG::run_flat(args.update_code, P, V, rot, U);
 #pragma unroll
                 for (uint32_t w = 0; w < 3; ++w) {
+                    // (with the nontemporal hint where plan::use_store_hints holds, as the per-particle path's plane stores: no difference on c2 or c4, three
+                    // rounds on one box - profiles/flat_store_hint_ab.log)
                     if (fl & 16u) pw[(step * 3u + w) * 64u + lane] = u4v{f2u(P[w][0]), f2u(P[w][1]), f2u(P[w][2]), f2u(P[w][3])};
                     if (fl & 32u) vw[(step * 3u + w) * 64u + lane] = u4v{f2u(V[w][0]), f2u(V[w][1]), f2u(V[w][2]), f2u(V[w][3])};
                 }

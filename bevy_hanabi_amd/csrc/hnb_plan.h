@@ -16,6 +16,8 @@
 //   partition_init_passes which init passes stay in front of the fork behind a heavy program's own init (parents first; nobody beside its update)
 //   set_lookup_due        when a context looks the set module of its small programs up (once per population, after two merged frames)
 //   split_uncovered       which programs a loaded set module does not know stay out of the shared launches (so that the others keep their set kernels)
+//   stage_ring_begin/_end which slot of the staging ring a frame's parameter block goes to, which event the host waits for before it writes the
+//                         slot, and behind which frames a completion event is recorded (one per group of frames, not one per frame)
 //
 // What each proof assumes about the device code is stated at the device side (hnb_kernels.hip.h); a wrong proof is reported by the
 // kernels through HnbEffectMetadata::fault, never silently.
@@ -378,6 +380,53 @@ inline bool use_streaming_hints(uint64_t total_slots, uint32_t update_bytes_per_
 // 8.4M particles writes 235 MB) is found there by the next frame's reversed walk, and the hint would throw that away (C3: +22 %).
 constexpr uint64_t kStoreHintBytes = 384ull << 20;
 inline bool use_store_hints(uint64_t total_slots, uint32_t stored_bytes_per_slot) { return total_slots * (uint64_t)stored_bytes_per_slot > kStoreHintBytes; }
+
+// ---- the staging ring of the frames' parameter blocks (ensure_stage / simulate_frame) -----------------------------------------------------------
+// A frame that has something to enqueue (a program with effects that no earlier fused launch covers) writes its parameter block into the next of
+// kStageSlots slots; its kernels read the slot. INVARIANT: the host rewrites a slot only after an event has completed that was recorded - on the
+// context's stream, whose order every launch of a frame joins before the frame ends - behind the last frame that read the slot, or after the
+// stream itself was waited for. One record per frame put a marker packet of its own behind every frame's last kernel; here ONE record closes a
+// group of kStageGroup staged frames (kStageGroups events), and the slot of a group's first frame waits for the record that closed the same group
+// one lap earlier: the host runs kStageSlots - kStageGroup + 1 .. kStageSlots staged frames ahead of the device.
+//   * Slots are counted in STAGED frames, not in context frames: a frame without anything to enqueue (no program has effects, or every program is
+//     covered by a fused launch of hnb_simulate_steps) takes no slot, waits for nothing and closes no group - so a group is never closed by an
+//     empty frame, and an open group's slots cannot come round again before three more staged frames have closed it.
+//   * A fused span is one staged frame: its launch reads the S parameter blocks from that frame's slot; the frames it covers stage nothing.
+//   * A frame that fails behind the write of its slot does not advance: some of its launches may be enqueued and read the slot the retry will
+//     rewrite. No event stands behind them: `torn`, and the next staged frame waits for the stream (stage_ring_drained).
+//   * Whoever waits for the stream for reasons of its own (the slots re-allocated because the block grew or the upload path changed) calls
+//     stage_ring_drained: nothing is outstanding, no event of an earlier lap is waited for again.
+constexpr uint32_t kStageSlots = 16, kStageGroup = 4, kStageGroups = kStageSlots / kStageGroup;
+constexpr int kStageWaitNone = -1, kStageWaitStream = -2;   // StageStep::wait otherwise: the index of the event to wait for
+struct StageRing {
+    uint32_t staged = 0;      // staged frames enqueued whole so far: the next one's slot is staged % kStageSlots (2^32 is a multiple of the ring)
+    uint32_t recorded = 0;    // bit g: event g stands behind the frames of group g's last lap and nobody has waited for the stream since
+    bool torn = false;        // a failed frame may have left readers of its slot behind no event
+};
+struct StageStep { uint32_t slot = 0; int wait = kStageWaitNone; };
+// in front of a frame's write of its slot (stages: the frame has something to enqueue)
+inline StageStep stage_ring_begin(const StageRing& r, bool stages) {
+    StageStep st;
+    if (!stages) return st;
+    st.slot = r.staged % kStageSlots;
+    const uint32_t g = st.slot / kStageGroup;
+    if (r.torn) st.wait = kStageWaitStream;
+    else if (st.slot % kStageGroup == 0u && (r.recorded >> g & 1u)) st.wait = (int)g;   // (the other slots of the group: its first frame has waited)
+    return st;
+}
+// the caller has waited for the context's stream
+inline void stage_ring_drained(StageRing& r) { r.recorded = 0u; r.torn = false; }
+// behind a frame. written: the slot was (or may have been) written and launches may have been enqueued; ok: the frame was enqueued whole and counts.
+// Returns the event to record behind the frame on the context's stream, or kStageWaitNone.
+inline int stage_ring_end(StageRing& r, bool stages, bool written, bool ok) {
+    if (!stages) return kStageWaitNone;
+    if (!ok) { r.torn = r.torn || written; return kStageWaitNone; }
+    const uint32_t slot = r.staged % kStageSlots, g = slot / kStageGroup;
+    r.staged += 1u;
+    if (slot % kStageGroup != kStageGroup - 1u) return kStageWaitNone;
+    r.recorded |= 1u << g;
+    return (int)g;
+}
 
 // ---- the plan of one program for one frame ------------------------------------------------------------------------------------------------
 struct FramePlan {
