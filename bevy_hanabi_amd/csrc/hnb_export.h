@@ -118,4 +118,48 @@ HNB_SORT_KEY_FN const uint32_t* export_order_of_instance(const ExportArgs& a, ui
     return a.order + ((size_t)k * 2u + export_sort_pass(st[0] & st[1], kExportSortPasses).src) * a.order_pitch;
 }
 
+
+// ---- filtered export (hnb_effect_export_filtered; kernels: hnb_export_filter.hip, a third code object) ----
+// A stable compaction of the alive list by a predicate, over tiles of the sort's size: mark (one bit per row, one count per tile), an exclusive scan of
+// the tile counts by one workgroup, compact (order[offset + rank] = slot). The gather then reads ExportArgs::order (one buffer, order_pitch unused) and
+// takes its row count from ExportArgs::order_state[0], the kept total. No workgroup waits for another.
+constexpr uint32_t kExportFilterTile = kExportSortTile;                  // rows per workgroup
+constexpr uint32_t kExportFilterTileWords = kExportFilterTile / 64u;     // 64-bit mask words per tile: one per wave and round
+
+struct ExportFilterArgs {
+    const uint64_t* slab;           // [1] the instance's slab base address
+    const HnbDeviceMeta* meta;      // [1] its row after the frames enqueued so far
+    uint32_t* order;                // [capacity] slots of the kept rows, in list order
+    uint64_t* mask;                 // [tiles][kExportFilterTileWords] bit r % 64 of word r / 64: list row r is kept
+    uint32_t* tile_count;           // [tiles] kept rows of a tile (k_export_filter_mark)
+    uint32_t* tile_offset;          // [tiles] kept rows of the tiles in front of it (k_export_filter_scan)
+    uint32_t* state;                // [0] = kept rows in all
+    uint64_t alive_off[2];          // bytes from the slab base
+    uint64_t plane_off;             // the predicate's source: the POSITION plane (PLANES, SPHERE) or the scalar attribute's
+    uint32_t capacity, tiles;
+    uint32_t kind;                  // HNB_FILTER_*
+    uint32_t n_planes, is_f32, invert, lo_bits, hi_bits;
+    float P[HNB_FILTER_MAX_PLANES][4];
+};
+
+// The scratch of an effect's filtered exports, one allocation; every section starts on a 256-byte boundary. 4 bytes per slot of capacity (order) and,
+// per tile of 4096 slots, 512 bytes of mask and two words.
+struct ExportFilterScratch { uint32_t tiles; uint64_t order_off, order_bytes, mask_off, mask_bytes, count_off, count_bytes, offset_off, offset_bytes, state_off, state_bytes, total; };
+HNB_SORT_KEY_FN ExportFilterScratch export_filter_scratch_layout(uint32_t capacity) {
+    ExportFilterScratch l;
+    l.tiles = (uint32_t)(((uint64_t)capacity + kExportFilterTile - 1u) / kExportFilterTile);
+    l.order_off = 0;
+    l.order_bytes = (uint64_t)capacity * 4u;
+    l.mask_off = (l.order_off + l.order_bytes + 255u) & ~(uint64_t)255u;
+    l.mask_bytes = (uint64_t)l.tiles * kExportFilterTileWords * 8u;
+    l.count_off = (l.mask_off + l.mask_bytes + 255u) & ~(uint64_t)255u;
+    l.count_bytes = (uint64_t)l.tiles * 4u;
+    l.offset_off = (l.count_off + l.count_bytes + 255u) & ~(uint64_t)255u;
+    l.offset_bytes = (uint64_t)l.tiles * 4u;
+    l.state_off = (l.offset_off + l.offset_bytes + 255u) & ~(uint64_t)255u;
+    l.state_bytes = 16u;
+    l.total = l.state_off + 256u;
+    return l;
+}
+
 }  // namespace hnb

@@ -1,6 +1,6 @@
 // The gather of the packed export (hnb_export.hip: k_export_rows_*, slots from the alive list; hnb_export_sort.hip: k_export_sort_rows_*, slots
-// from the order a sorted export produced; k_export_sort_rows_inst_* / _all_*: the two scopes of the sorted program export). One body; the
-// instantiations by where a row's slot comes from.
+// from the order a sorted export produced; k_export_sort_rows_inst_* / _all_*: the two scopes of the sorted program export; hnb_export_filter.hip:
+// k_export_filter_rows_*, the slots a filtered export kept). One body; the instantiations by where a row's slot comes from.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -40,7 +40,8 @@ __device__ __forceinline__ void store_field(uint32_t* rec, const ExportFieldArg 
 //   kRowsOrderedInstance   instance blockIdx.y's section of the sorted program export's value buffers (export_order_of_instance)
 //   kRowsOrderedProgram    one order over all instances: order[r] names (instance, slot); the rows are those of the concatenated space, the
 //                          instance's slab and slot base are taken per lane
-constexpr uint32_t kRowsList = 0, kRowsOrdered = 1, kRowsOrderedInstance = 2, kRowsOrderedProgram = 3;
+//   kRowsFiltered          order[r], the slots a filtered export kept (one buffer); the rows are order_state[0], the kept total, not alive_count
+constexpr uint32_t kRowsList = 0, kRowsOrdered = 1, kRowsOrderedInstance = 2, kRowsOrderedProgram = 3, kRowsFiltered = 4;
 template <uint32_t LDS_DWORDS, uint32_t ORDER>
 __device__ __forceinline__ void export_rows(const ExportArgs& a) {
     __shared__ __attribute__((aligned(16))) uint32_t image[LDS_DWORDS];
@@ -50,6 +51,10 @@ __device__ __forceinline__ void export_rows(const ExportArgs& a) {
     if constexpr (ORDER == kRowsOrderedProgram) {                                 // every instance's rows; the sort bounded them the same way
         const uint32_t all = a.offsets[a.n_inst];
         n = all < a.total_cap ? all : a.total_cap;
+    }
+    if constexpr (ORDER == kRowsFiltered) {                                       // the rows the filter kept; the compaction bounded them the same way
+        const uint32_t kept = a.order_state[0];
+        n = kept < a.capacity ? kept : a.capacity;
     }
     const uint32_t row0 = blockIdx.x * a.tile_rows;
     if (a.out_count && blockIdx.x == 0u && tid == 0u) {                           // (effect form only)
@@ -78,6 +83,9 @@ __device__ __forceinline__ void export_rows(const ExportArgs& a) {
             if (ki >= a.n_inst) ki = a.n_inst - 1u;                               // (the sort packed only pairs inside the program; nothing is read outside it whatever the buffer holds)
             if (slot >= a.capacity) slot = a.capacity - 1u;
             base = reinterpret_cast<const char*>(a.slabs[ki]);
+        } else if constexpr (ORDER == kRowsFiltered) {
+            slot = a.order[row0 + tid];
+            if (slot >= a.capacity) slot = a.capacity - 1u;                       // (the compaction wrote list entries; nothing is read outside the planes whatever the buffer holds)
         } else slot = list[ring_index(head, row0 + tid, a.capacity)];
         const uint32_t id = (a.slot_bases ? a.slot_bases[ki] : a.slot_base) + slot;
         uint32_t* rec = image + tid * sdw;

@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "hnb_simulate_steps", "hnb_effect_set_frames_ahead", "hnb_program_set_frames_ahead", "hnb_ctx_step_stats",
     "hnb_program_prepare_steps", "hnb_jit_precompile_steps",
     "hnb_effect_export", "hnb_program_export", "hnb_effect_export_sorted", "hnb_program_export_sorted",
+    "hnb_effect_export_filtered",
 ]
 
 # hnb_ctx_set_option (include/hanabi_amd.h): name -> option id
@@ -174,6 +175,42 @@ def export_sort(key, v=(0, 0, 0), attr=0, descending=False):
     return s
 
 
+FILTER_PLANES, FILTER_SPHERE, FILTER_ATTR_RANGE = 0, 1, 2   # HNB_FILTER_*
+FILTER_MAX_PLANES = 6                                        # HNB_FILTER_MAX_PLANES
+FILTER_KINDS = {"planes": FILTER_PLANES, "sphere": FILTER_SPHERE, "attr_range": FILTER_ATTR_RANGE}
+
+
+class ExportFilter(C.Structure):
+    """HnbExportFilter (hnb_effect_export_filtered): the predicate in front of the export."""
+    _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_uint32), ("n_planes", C.c_uint32), ("attr", C.c_uint32), ("invert", C.c_uint32),
+                ("lo_bits", C.c_uint32), ("hi_bits", C.c_uint32), ("reserved", C.c_uint32), ("P", (C.c_float * 4) * FILTER_MAX_PLANES)]
+
+
+def _scalar_bits(x):
+    """A bound of an attribute range as the 32 bits the library compares: a Python float as binary32, an int as it is."""
+    if isinstance(x, (float, np.floating)):
+        return int(np.array([x], np.float32).view(np.uint32)[0])
+    return int(x) & 0xFFFFFFFF
+
+
+def export_filter(kind, planes=(), sphere=None, attr=0, lo=0, hi=0, invert=False):
+    """kind: "planes" | "sphere" | "attr_range" or a HNB_FILTER_* value -> ExportFilter. planes: up to six (a, b, c, d); sphere: (cx, cy, cz, squared
+    radius); lo / hi: floats (taken as binary32) or ints (taken as bit patterns). More than six planes keep their count: the library refuses them."""
+    f = ExportFilter()
+    f.struct_size = C.sizeof(ExportFilter)
+    f.kind = FILTER_KINDS[kind] if isinstance(kind, str) else int(kind)
+    rows = [tuple(r) for r in planes]
+    f.n_planes = len(rows)
+    if sphere is not None:
+        rows = [tuple(sphere)] + rows[1:]
+    for i, r in enumerate(rows[:FILTER_MAX_PLANES]):
+        f.P[i] = (C.c_float * 4)(*[float(x) for x in r])
+    f.attr = int(attr)
+    f.lo_bits, f.hi_bits = _scalar_bits(lo), _scalar_bits(hi)
+    f.invert = int(invert)
+    return f
+
+
 _lib = None
 
 
@@ -241,6 +278,7 @@ def load_library():
         lib.hnb_program_export.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.c_void_p]
         lib.hnb_effect_export_sorted.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.POINTER(ExportSort)]
         lib.hnb_program_export_sorted.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.POINTER(ExportSort), C.c_uint32, C.c_void_p]
+        lib.hnb_effect_export_filtered.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.POINTER(ExportFilter)]
         _lib = lib
     return _lib
 
@@ -591,6 +629,14 @@ class Effect:
         d = export_desc(fields, dst_ptr, stride, capacity_records, count_ptr)
         s = export_sort(key, v, attr, descending)
         _check(self._lib.hnb_effect_export_sorted(self._h, C.byref(d), C.byref(s)))
+
+    def export_filtered(self, fields, dst_ptr, stride, capacity_records, count_ptr=None, *, kind, planes=(), sphere=None, attr=0, lo=0, hi=0, invert=False):
+        """hnb_effect_export_filtered: the records of export() for the rows a predicate keeps, in list order - kind "planes" (inside every half-space
+        a*x + b*y + c*z + d >= 0 of `planes`), "sphere" ((cx, cy, cz, squared radius)) or "attr_range" (lo <= the scalar attribute `attr` <= hi,
+        floats as binary32, ints as bit patterns); invert keeps the other rows. count_ptr: [0] = records written, [1] = rows kept."""
+        d = export_desc(fields, dst_ptr, stride, capacity_records, count_ptr)
+        f = export_filter(kind, planes, sphere, attr, lo, hi, invert)
+        _check(self._lib.hnb_effect_export_filtered(self._h, C.byref(d), C.byref(f)))
 
     def check(self):
         """hnb_effect_check: list permutation, alive bytes, age < lifetime, fault flag - on the device; a dict with "ok"."""

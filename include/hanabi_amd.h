@@ -662,6 +662,57 @@ int hnb_effect_export_sorted(HnbEffect* fx, const HnbExportDesc* desc, const Hnb
 int hnb_program_export_sorted(HnbProgram* prog, const HnbExportDesc* desc, const HnbExportSort* sort,
                               uint32_t scope, uint32_t* out_offsets /* device [n_instances + 1], may be NULL */);
 
+/* Filtered export: hnb_effect_export with a predicate in front - the particles inside a frustum or near a camera, the ones of one ribbon or
+ * younger than some age - for a consumer that would otherwise export every alive particle and discard most of them.
+ * Records
+ *   Record r is the r-th row of the alive list THAT THE FILTER KEEPS, in list order: the compaction is stable. What a record holds, the zeroed
+ *   padding, HNB_ATTR_ID, ring lists read through their head and the asynchronous contract (enqueued on the simulation stream behind the frames
+ *   enqueued so far, no host synchronisation, no readback, counts and list head read from the HnbDeviceMeta row on the device) are
+ *   hnb_effect_export's. With a filter that keeps every row, dst is byte for byte what hnb_effect_export writes.
+ * Counts and clamp
+ *   out_count[0] = the records written, min(kept, dst_capacity_records); out_count[1] = the rows kept. Records at and past the written count are
+ *   not touched. A destination of K records gets the FIRST K kept rows of list order.
+ * Predicates (p = POSITION as stored; no transform is applied: the caller brings planes and centres into the effect's simulation space, and folds
+ * a particle radius into P[i][3] or into the squared radius). Every f32 operation is rounded on its own, in the order written; nothing is
+ * contracted into a fused multiply-add - a binary32 restatement on the host gives the same bits. A comparison with a NaN is false: the row does
+ * not pass, and with `invert` it is kept.
+ *   HNB_FILTER_PLANES      pass iff for every i < n_planes: ((p.x*P[i][0] + p.y*P[i][1]) + p.z*P[i][2]) + P[i][3] >= 0
+ *   HNB_FILTER_SPHERE      e = p - P[0][0..2] per component; pass iff (e.x*e.x + e.y*e.y) + e.z*e.z <= P[0][3]
+ *   HNB_FILTER_ATTR_RANGE  pass iff key(lo_bits) <= key(value) <= key(hi_bits), value = the scalar attribute `attr` as stored, key = the sorted
+ *                          export's ascending key: an f32 attribute in its total order (-NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN, so a NaN
+ *                          is a key like any other here), every other scalar type by its bits as an unsigned number
+ *   `invert` keeps exactly the rows that do not pass.
+ * State
+ *   The simulation is only read: lists, planes and every later frame are bit for bit what they would be without the call. Stale AGE is
+ *   materialised first when AGE is a record field OR the ATTR_RANGE source.
+ * Errors: HNB_ERR_INVALID_ARG (with hnb_last_error text; nothing is enqueued) for everything hnb_effect_export rejects, and for: filter NULL, another
+ *   struct_size, an unknown kind, reserved not 0, invert above 1, n_planes outside 1..HNB_FILTER_MAX_PLANES for PLANES or not 0 for the other
+ *   kinds, a plane or sphere coefficient that is not finite, PLANES / SPHERE on a program whose layout lacks POSITION, ATTR_RANGE with an attribute
+ *   the layout lacks, with one of more than one component, or with HNB_ATTR_ID / HNB_ATTR_PARTICLE_COUNTER (which have no plane), and
+ *   key(lo_bits) > key(hi_bits).
+ * Scratch: owned by the library, per effect: 4 bytes per slot of capacity (the kept rows' slots) plus 520 bytes per 4096 slots (one bit per row,
+ *   two words per tile). Allocated by the effect's FIRST filtered export - that one call may synchronise the device once for the allocation - and
+ *   freed with the effect. Exports of one effect reuse it in stream order. The scratch of hnb_effect_export_sorted is another allocation: the two
+ *   calls do not disturb each other.
+ * The kernels (mark, a one-workgroup scan of the tile counts, compact - no workgroup waits for another - and the gather of hnb_effect_export fed
+ *   from the result) live in a third code object that the library carries and loads on first use; HNB_ERR_HIP if it cannot be loaded. */
+#define HNB_FILTER_PLANES     0u   /* pass iff for every i < n_planes: ((p.x*P[i][0] + p.y*P[i][1]) + p.z*P[i][2]) + P[i][3] >= 0 */
+#define HNB_FILTER_SPHERE     1u   /* e = p - P[0][0..2] per component; pass iff (e.x*e.x + e.y*e.y) + e.z*e.z <= P[0][3] */
+#define HNB_FILTER_ATTR_RANGE 2u   /* pass iff key(lo_bits) <= key(value) <= key(hi_bits): the scalar attribute `attr` as stored */
+#define HNB_FILTER_MAX_PLANES 6u
+typedef struct HnbExportFilter {
+    uint32_t struct_size;   /* sizeof(HnbExportFilter) of the caller */
+    uint32_t kind;          /* HNB_FILTER_* */
+    uint32_t n_planes;      /* PLANES: 1..HNB_FILTER_MAX_PLANES; otherwise 0 */
+    uint32_t attr;          /* ATTR_RANGE: HnbAttr; otherwise 0 */
+    uint32_t invert;        /* 0: keep the rows that pass; 1: keep the rows that do not */
+    uint32_t lo_bits;       /* ATTR_RANGE: the bounds as bit patterns of the attribute's scalar type, both inclusive; otherwise 0 */
+    uint32_t hi_bits;
+    uint32_t reserved;      /* 0 */
+    float    P[HNB_FILTER_MAX_PLANES][4];   /* PLANES: (a, b, c, d) per plane; SPHERE: P[0] = (centre, squared radius) */
+} HnbExportFilter;
+int hnb_effect_export_filtered(HnbEffect* fx, const HnbExportDesc* desc, const HnbExportFilter* filter);
+
 /* Readback (synchronising; reporting / parity only, never on the frame path). */
 int hnb_effect_metadata(HnbEffect* fx, HnbEffectMetadata* out);
 int hnb_effect_alive_count(HnbEffect* fx, uint32_t* out);
