@@ -1,5 +1,8 @@
-// Kernel arguments of the packed export (hnb_effect_export / hnb_program_export, include/hanabi_amd.h "Packed output"): shared by the
-// kernels' translation unit (hnb_export.hip, a code object of its own) and the runtime that loads and launches them (hanabi_amd.hip).
+// The packed exports (hnb_effect_export, hnb_program_export, their _sorted forms, hnb_effect_export_filtered; include/hanabi_amd.h "Packed output"),
+// shared by the kernels' translation units (hnb_export.hip, hnb_export_sort.hip, hnb_export_filter.hip: a code object each) and the runtime that loads
+// and launches them (hanabi_amd.hip): the kernels' argument blocks, the sort's pass and (instance, slot) arithmetic, the scratch layouts of the sort and
+// the filter, the kernels by name (ExportKernel) and the launches of a call (export_launch_plan). Plain C++ below the argument blocks: a host compiler
+// takes it, so the tests check the layouts and the plan without a GPU.
 #pragma once
 #include <stdint.h>
 
@@ -160,6 +163,99 @@ HNB_SORT_KEY_FN ExportFilterScratch export_filter_scratch_layout(uint32_t capaci
     l.state_bytes = 16u;
     l.total = l.state_off + 256u;
     return l;
+}
+
+// The scratch of a sorted export, one allocation; every section starts on a 256-byte boundary. `sections` sections of `rows` rows in every buffer:
+// u32 keys[sections][2][pitch], u32 vals likewise (16 bytes per row), then - all of it zeroed in front of every multi-tile sort - an ExportSortState and
+// u32 gsum[2][4][groups][256] per section, and last u32 hist[4][tiles][256] per section, which the kernels write before they read it. Instance scope:
+// one section of `capacity` rows per instance (an effect's own sort is n_inst = 1). Program scope: one section of n_inst * capacity rows.
+// rows == 0: more than 0xFFFFFF00 rows in a section, which 32 bits of pitch do not hold.
+struct ExportSortScratch { uint32_t sections, rows, pitch, tiles, groups; uint64_t vals_off, state_off, gsum_off, hist_off, zero_bytes, total; };
+HNB_SORT_KEY_FN ExportSortScratch export_sort_scratch_layout(uint32_t n_inst, uint32_t capacity, uint32_t scope) {
+    ExportSortScratch l = {};
+    const uint64_t rows = scope == HNB_SORT_SCOPE_PROGRAM ? (uint64_t)n_inst * capacity : capacity;
+    if (rows > 0xFFFFFF00ull) return l;
+    l.sections = scope == HNB_SORT_SCOPE_PROGRAM ? 1u : n_inst;
+    l.rows = (uint32_t)rows;
+    l.pitch = (l.rows + 63u) & ~63u;
+    l.tiles = (uint32_t)((rows + kExportSortTile - 1u) / kExportSortTile);       // (in 64 bits: the last 4095 row counts would wrap)
+    l.groups = (l.tiles + kExportSortGroup - 1u) / kExportSortGroup;
+    l.vals_off = (uint64_t)l.sections * l.pitch * 8u;
+    l.state_off = l.vals_off * 2u;
+    l.gsum_off = l.state_off + (((uint64_t)l.sections * sizeof(ExportSortState) + 255u) & ~(uint64_t)255u);
+    l.hist_off = l.gsum_off + (uint64_t)l.sections * 2u * kExportSortPasses * l.groups * 1024u;
+    l.zero_bytes = l.hist_off - l.state_off;
+    l.total = l.hist_off + (uint64_t)l.sections * kExportSortPasses * l.tiles * 1024u;
+    return l;
+}
+
+
+// ---- the host path of every form: which kernels there are, and which of them a call launches ----
+// The kernels of the three code objects, in the order of their units: the index of a kernel's handle in the context.
+enum ExportUnit : uint32_t { kUnitExport, kUnitExportSort, kUnitExportFilter, kExportUnits };
+enum ExportKernel : uint32_t {
+    kExpRows0, kExpRows1, kExpRows2, kExpRows3, kExpOffsets,                                                    // hnb_export.hip
+    kExpSortRows0, kExpSortRows1, kExpSortRows2, kExpSortRows3, kExpSortTile, kExpSortKeys, kExpSortHist, kExpSortScatter,   // hnb_export_sort.hip: one effect,
+    kExpSortRowsInst0, kExpSortRowsInst1, kExpSortRowsInst2, kExpSortRowsInst3, kExpSortTileInst, kExpSortKeysInst, kExpSortHistInst, kExpSortScatterInst,   // (tiles, instances),
+    kExpSortRowsAll0, kExpSortRowsAll1, kExpSortRowsAll2, kExpSortRowsAll3, kExpSortFill, kExpSortHistAll, kExpSortScatterAll,   // all instances' rows as one space
+    kExpFilterRows0, kExpFilterRows1, kExpFilterRows2, kExpFilterRows3, kExpFilterTile, kExpFilterMark, kExpFilterScan, kExpFilterCompact,   // hnb_export_filter.hip
+    kExpKernels
+};
+
+enum ExportForm : uint32_t { kExportPlain, kExportSorted, kExportFiltered };
+// What a launch passes: an argument block by value (the sort's hist and scatter kernels take the pass behind it), or k_export_offsets' five words
+enum ExportArgBlock : uint32_t { kExportArgsRows, kExportArgsSort, kExportArgsSortPass, kExportArgsFilter, kExportArgsOffsets };
+struct ExportLaunch { uint32_t kernel, grid_x, grid_y, args, pass; };   // (workgroups of kExportBlock lanes)
+constexpr uint32_t kExportPlanMax = 12, kExportNoMemset = ~0u;
+struct ExportPlan {
+    uint32_t n;                         // launches, in stream order
+    uint32_t memset_before;             // a multi-tile sort: bytes [zero_off, zero_off + zero_bytes) of the sort's scratch are zeroed in front of launch
+    uint64_t zero_off, zero_bytes;      //   `memset_before` (the state words and group sums); kExportNoMemset: nothing is
+    ExportLaunch launch[kExportPlanMax];
+};
+
+// The gather of a form, by the LDS image of its records (export_variant)
+HNB_SORT_KEY_FN uint32_t export_rows_kernel(uint32_t form, bool program, uint32_t scope, uint32_t variant) {
+    const uint32_t first = form == kExportFiltered ? kExpFilterRows0 : form == kExportPlain ? kExpRows0 : !program ? kExpSortRows0 :
+                           scope == HNB_SORT_SCOPE_PROGRAM ? kExpSortRowsAll0 : kExpSortRowsInst0;
+    return first + variant;
+}
+
+// The launches of one export, in order. `program`: all n_inst instances of a program (plain or sorted in `scope`), else one effect (n_inst and scope
+// are not read). A sorted form's rows must fit (export_sort_scratch_layout(...).rows != 0). Decides; hanabi_amd.hip run_export_plan executes.
+HNB_SORT_KEY_FN ExportPlan export_launch_plan(uint32_t form, bool program, uint32_t scope, uint32_t n_inst, uint32_t capacity, uint32_t stride_bytes) {
+    ExportPlan pl = {};
+    pl.memset_before = kExportNoMemset;
+    const uint32_t n = program ? n_inst : 1u;
+    const bool all = program && form == kExportSorted && scope == HNB_SORT_SCOPE_PROGRAM;
+    const uint32_t tiles = (uint32_t)(((uint64_t)capacity + kExportSortTile - 1u) / kExportSortTile);   // of one instance (the filter's tiles are the sort's)
+    const uint32_t rows = all ? n * capacity : capacity, gy = all ? 1u : n;        // of the gather's row space, and how many of them
+    const uint32_t variant = export_variant(stride_bytes), tile_rows = export_tile_rows(variant);
+    const auto add = [&pl](uint32_t kernel, uint32_t gx, uint32_t gy, uint32_t args, uint32_t pass = 0u) { pl.launch[pl.n++] = ExportLaunch{kernel, gx, gy, args, pass}; };
+    if (program) add(kExpOffsets, 1u, 1u, kExportArgsOffsets);
+    if (form == kExportSorted) {
+        const ExportSortScratch l = export_sort_scratch_layout(n, capacity, all ? HNB_SORT_SCOPE_PROGRAM : HNB_SORT_SCOPE_INSTANCE);
+        const uint32_t tile = program ? kExpSortTileInst : kExpSortTile, keys = all ? kExpSortFill : program ? kExpSortKeysInst : kExpSortKeys;
+        const uint32_t hist = all ? kExpSortHistAll : program ? kExpSortHistInst : kExpSortHist, scatter = all ? kExpSortScatterAll : program ? kExpSortScatterInst : kExpSortScatter;
+        if (!all && l.tiles <= 1u) add(tile, 1u, n, kExportArgsSort);              // every instance's whole sort by one workgroup
+        else {
+            pl.memset_before = pl.n; pl.zero_off = l.state_off; pl.zero_bytes = l.zero_bytes;
+            add(keys, tiles, n, kExportArgsSort);                                  // (the keys kernels count pass 0's digits; k_export_sort_fill does not)
+            for (uint32_t pass = 0; pass < kExportSortPasses; ++pass) {
+                if (pass || all) add(hist, l.tiles, gy, kExportArgsSortPass, pass);
+                add(scatter, l.tiles, gy, kExportArgsSortPass, pass);
+            }
+        }
+    } else if (form == kExportFiltered) {
+        if (tiles <= 1u) add(kExpFilterTile, 1u, 1u, kExportArgsFilter);           // mark, count and compact by one workgroup
+        else {
+            add(kExpFilterMark, tiles, 1u, kExportArgsFilter);
+            add(kExpFilterScan, 1u, 1u, kExportArgsFilter);
+            add(kExpFilterCompact, tiles, 1u, kExportArgsFilter);
+        }
+    }
+    add(export_rows_kernel(form, program, scope, variant), (rows + tile_rows - 1u) / tile_rows, gy, kExportArgsRows);
+    return pl;
 }
 
 }  // namespace hnb

@@ -328,3 +328,167 @@ def test_scratch_layout_sections_do_not_overlap_and_stay_inside(tmp_path):
             end = off + size
         assert end <= total, (cap, sections, total)
         assert total <= 4 * cap + 520 * tiles + 6 * 256                  # 4 bytes per slot, 520 per tile, the alignment
+
+
+# ---- the sort's scratch layout and the launch plan of every form (csrc/hnb_export.h), as stand-alone host programs --------------------------------
+def _standalone(tmp_path, name, src):
+    """g++ alone, with the address and undefined-behaviour sanitizers: the header is plain C++ on the host"""
+    (tmp_path / f"{name}.cpp").write_text(src)
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I" + CSRC, "-I" + os.path.join(ROOT, "include"),
+                           str(tmp_path / f"{name}.cpp"), "-o", str(tmp_path / name)])
+    return str(tmp_path / name)
+
+
+SORT_ROWS_MAX = 0xFFFFFF00
+INSTANCE, PROGRAM = 0, 1
+
+
+def sort_layout(n_inst, cap, scope):
+    """export_sort_scratch_layout restated: (sections, rows, pitch, tiles, groups, vals_off, state_off, gsum_off, hist_off, zero_bytes, total)"""
+    rows = n_inst * cap if scope == PROGRAM else cap
+    if rows > SORT_ROWS_MAX:
+        return (0,) * 11
+    sections = 1 if scope == PROGRAM else n_inst
+    pitch, tiles = (rows + 63) & ~63, -(-rows // 4096)
+    groups = -(-tiles // 32)
+    vals_off = sections * pitch * 8
+    state_off = 2 * vals_off
+    gsum_off = state_off + ((sections * 16 + 255) & ~255)
+    hist_off = gsum_off + sections * 8192 * groups
+    return (sections, rows, pitch, tiles, groups, vals_off, state_off, gsum_off, hist_off, hist_off - state_off, hist_off + sections * 4096 * tiles)
+
+
+def test_sort_scratch_layout_sections_are_ordered_aligned_and_the_effect_layout_is_the_one_instance_case(tmp_path):
+    assert runtime.SORT_SCOPE_INSTANCE == INSTANCE and runtime.SORT_SCOPE_PROGRAM == PROGRAM
+    exe = _standalone(tmp_path, "sl", r"""
+    #include <cstdio>
+    #include <cstdint>
+    #include "hnb_export.h"
+    int main() {
+        unsigned long long n, cap, scope;
+        while (std::scanf("%llu %llu %llu", &n, &cap, &scope) == 3) {
+            const hnb::ExportSortScratch l = hnb::export_sort_scratch_layout((uint32_t)n, (uint32_t)cap, (uint32_t)scope);
+            std::printf("%u %u %u %u %u %llu %llu %llu %llu %llu %llu\n", l.sections, l.rows, l.pitch, l.tiles, l.groups, (unsigned long long)l.vals_off, (unsigned long long)l.state_off,
+                        (unsigned long long)l.gsum_off, (unsigned long long)l.hist_off, (unsigned long long)l.zero_bytes, (unsigned long long)l.total);
+        }
+        return 0;
+    }
+    """)
+    caps = [1, 63, 64, 300, 4095, 4096, 4097, 10_000, 131_072, 131_073, 16_777_216, SORT_ROWS_MAX]
+    cases = [(n, cap, scope) for cap in caps for n in (1, 5) for scope in (INSTANCE, PROGRAM)] + [(1, SORT_ROWS_MAX + 1, INSTANCE), (5, SORT_ROWS_MAX + 1, INSTANCE), (65535, 16_777_216, PROGRAM)]
+    out = subprocess.run([exe], input="\n".join("%d %d %d" % c for c in cases), capture_output=True, text=True, check=True).stdout.splitlines()
+    assert len(out) == len(cases)
+    for (n, cap, scope), line in zip(cases, out):
+        got = tuple(int(x) for x in line.split())
+        sections, rows, pitch, tiles, groups, vals_off, state_off, gsum_off, hist_off, zero_bytes, total = got
+        want_rows = n * cap if scope == PROGRAM else cap
+        if want_rows > SORT_ROWS_MAX:
+            assert rows == 0, (n, cap, scope, got)                       # refused: 32 bits of pitch do not hold the section
+            continue
+        assert rows == want_rows and sections == (1 if scope == PROGRAM else n), (n, cap, scope, got)
+        assert pitch >= rows and pitch % 64 == 0 and tiles == -(-rows // 4096) and groups == -(-tiles // 32), (n, cap, scope, got)
+        # (offset, bytes) in the order of the allocation: keys, vals, state, gsum, hist
+        sects = [(0, sections * 2 * pitch * 4), (vals_off, sections * 2 * pitch * 4), (state_off, sections * 16), (gsum_off, sections * 2 * 4 * groups * 1024), (hist_off, sections * 4 * tiles * 1024)]
+        end = 0
+        for off, size in sects:
+            assert off >= end and off % 256 == 0 and size > 0, (n, cap, scope, sects)
+            end = off + size
+        assert end == total, (n, cap, scope, sects, total)               # total covers hist, and no more
+        assert state_off + zero_bytes == hist_off and gsum_off + sects[3][1] == hist_off, (n, cap, scope, got)   # the memset: state and gsum, exactly
+        assert got == sort_layout(n, cap, scope), (n, cap, scope, got)
+        if n == 1 and scope == INSTANCE:                                 # the closed forms of the effect form's own layout
+            p = (cap + 63) & ~63
+            assert (pitch, vals_off, state_off, gsum_off, hist_off, total) == (p, 8 * p, 16 * p, 16 * p + 256, 16 * p + 256 + 8192 * groups, 16 * p + 256 + 8192 * groups + 4096 * tiles)
+    assert (131_072 // 4096, sort_layout(1, 131_072, INSTANCE)[4], sort_layout(1, 131_073, INSTANCE)[4]) == (32, 1, 2)   # where a second group of tiles starts
+
+
+def plan_table(form, program, scope, n, cap, stride):
+    """The launches of an export as the design states them: ([(kernel, grid x, grid y, argument block, pass)], index of the launch behind the memset or None)"""
+    T = -(-cap // 4096)
+    v = {32: 0, 64: 1, 128: 2, 256: 3}[stride]
+    tile_rows = 128 if v == 3 else 256
+    whole = program and form == "sorted" and scope == PROGRAM
+    rows = n * cap if whole else cap
+    G, Tp = -(-rows // tile_rows), -(-rows // 4096)
+    if not program:
+        n = 1
+    L, memset = [], None
+    if program:
+        L.append(("kExpOffsets", 1, 1, "offsets", 0))
+    if form == "plain":
+        L.append((f"kExpRows{v}", G, n, "rows", 0))
+    elif form == "filtered":
+        if T <= 1:
+            L.append(("kExpFilterTile", 1, 1, "filter", 0))
+        else:
+            L += [("kExpFilterMark", T, 1, "filter", 0), ("kExpFilterScan", 1, 1, "filter", 0), ("kExpFilterCompact", T, 1, "filter", 0)]
+        L.append((f"kExpFilterRows{v}", G, 1, "rows", 0))
+    elif whole:
+        memset = len(L)
+        L.append(("kExpSortFill", T, n, "sort", 0))
+        for p in range(4):
+            L += [("kExpSortHistAll", Tp, 1, "sort+pass", p), ("kExpSortScatterAll", Tp, 1, "sort+pass", p)]
+        L.append((f"kExpSortRowsAll{v}", G, 1, "rows", 0))
+    else:
+        sfx = "Inst" if program else ""
+        if T <= 1:
+            L.append((f"kExpSortTile{sfx}", 1, n, "sort", 0))
+        else:
+            memset = len(L)
+            L += [(f"kExpSortKeys{sfx}", T, n, "sort", 0), (f"kExpSortScatter{sfx}", T, n, "sort+pass", 0)]
+            for p in (1, 2, 3):
+                L += [(f"kExpSortHist{sfx}", T, n, "sort+pass", p), (f"kExpSortScatter{sfx}", T, n, "sort+pass", p)]
+        L.append((f"kExpSortRows{sfx}{v}", G, n, "rows", 0))
+    return L, memset
+
+
+def test_launch_plan_of_every_form_is_the_designs_table(tmp_path):
+    kernels = (["kExpOffsets"] + [f"kExp{f}Rows{s}{v}" for f, s in (("", ""), ("Sort", ""), ("Sort", "Inst"), ("Sort", "All"), ("Filter", "")) for v in range(4)]
+               + [f"kExpSort{k}{s}" for s in ("", "Inst") for k in ("Tile", "Keys", "Hist", "Scatter")] + ["kExpSortFill", "kExpSortHistAll", "kExpSortScatterAll"]
+               + [f"kExpFilter{k}" for k in ("Tile", "Mark", "Scan", "Compact")])
+    assert len(kernels) == len(set(kernels)) == 5 + 23 + 8
+    exe = _standalone(tmp_path, "pl", r"""
+    #include <cstdio>
+    #include <cstdint>
+    #include "hnb_export.h"
+    using namespace hnb;
+    static const char* kernel_name(uint32_t k) {
+        switch (k) {
+    """ + "\n".join(f'        case {k}: return "{k}";' for k in kernels) + r"""
+        }
+        return "?";
+    }
+    int main() {
+        static_assert(kExpKernels == """ + str(len(kernels)) + r""", "every kernel has a name here");
+        static const char* const args[] = {"rows", "sort", "sort+pass", "filter", "offsets"};
+        static_assert(kExportArgsRows == 0 && kExportArgsSort == 1 && kExportArgsSortPass == 2 && kExportArgsFilter == 3 && kExportArgsOffsets == 4, "args[]");
+        unsigned form, program, scope, n, cap, stride;
+        while (std::scanf("%u %u %u %u %u %u", &form, &program, &scope, &n, &cap, &stride) == 6) {
+            const ExportPlan pl = export_launch_plan(form, program != 0, scope, n, cap, stride);
+            if (pl.n > kExportPlanMax) return 2;
+            std::printf("%u %d %llu %llu", pl.n, pl.memset_before == kExportNoMemset ? -1 : (int)pl.memset_before, (unsigned long long)pl.zero_off, (unsigned long long)pl.zero_bytes);
+            for (uint32_t i = 0; i < pl.n; ++i) std::printf(" %s %u %u %s %u", kernel_name(pl.launch[i].kernel), pl.launch[i].grid_x, pl.launch[i].grid_y, args[pl.launch[i].args], pl.launch[i].pass);
+            std::printf("\n");
+        }
+        return 0;
+    }
+    """)
+    forms = {"plain": 0, "sorted": 1, "filtered": 2}
+    rows_of_the_table = [("plain", 0, INSTANCE), ("plain", 1, INSTANCE), ("sorted", 0, INSTANCE), ("sorted", 1, INSTANCE), ("sorted", 1, PROGRAM), ("filtered", 0, INSTANCE)]
+    cases = [(form, program, scope, n, cap, stride) for form, program, scope in rows_of_the_table for cap in (300, 4096, 4097, 10_000) for n in (1, 5) for stride in (32, 256)]
+    assert ("sorted", 1, PROGRAM, 5, 300, 32) in cases                   # n * capacity <= 4096: still the fill / hist_all path
+    out = subprocess.run([exe], input="\n".join("%d %d %d %d %d %d" % ((forms[c[0]],) + c[1:]) for c in cases), capture_output=True, text=True, check=True).stdout.splitlines()
+    assert len(out) == len(cases)
+    for case, line in zip(cases, out):
+        form, program, scope, n, cap, stride = case
+        w = line.split()
+        count, memset, zero_off, zero_bytes = int(w[0]), int(w[1]), int(w[2]), int(w[3])
+        got = [(w[i], int(w[i + 1]), int(w[i + 2]), w[i + 3], int(w[i + 4])) for i in range(4, len(w), 5)]
+        want, want_memset = plan_table(*case)
+        assert count == len(got) <= 12 and got == want, (case, got, want)
+        assert memset == (-1 if want_memset is None else want_memset), (case, memset, want_memset)
+        if want_memset is not None:
+            l = sort_layout(n if program else 1, cap, scope)
+            assert (zero_off, zero_bytes) == (l[6], l[9]), (case, zero_off, zero_bytes, l)
+    whole_small = dict(zip(cases, out))[("sorted", 1, PROGRAM, 5, 300, 32)].split()
+    assert whole_small[4] == "kExpOffsets" and whole_small[9] == "kExpSortFill" and whole_small[1] == "1" and "kExpSortTileInst" not in whole_small

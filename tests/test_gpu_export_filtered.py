@@ -12,7 +12,8 @@ from bevy_hanabi_amd import effects, runtime
 from helpers import A, GpuRunner, assert_same_state, frame_seed
 from test_export_filtered_abi import FMA_P, FMA_PLANE, FMA_SPHERE, FMA_SPHERE_P, pass_planes, pass_range, pass_sphere
 from test_gpu_export import POS_AGE_LIFE_VEL, SENTINEL, Export, _device_meta, assert_export, expected_records, step
-from test_gpu_export_sorted import burst_then_die_off, expected_sorted, make, run_sorted
+import test_gpu_program_export_sorted as pes
+from test_gpu_export_sorted import DIR, burst_then_die_off, expected_sorted, make, run_sorted
 
 pytestmark = pytest.mark.gpu
 
@@ -538,4 +539,52 @@ def test_argument_errors_enqueue_nothing():
     ctx.synchronize()
     rec, mask = expected_filtered(fx, POS_AGE_LIFE_VEL, 32, **HALF)
     assert_export(ex, rec, "after the refusals", alive_rows=int(mask.sum()))
+    ctx.close()
+
+
+# ---- every form on one context ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("cap", [4097, 300], ids=["two_sort_tiles", "one_workgroup"])
+def test_every_export_form_interleaved_on_one_context(cap):
+    """One context, one program of three instances with 37, 0 and `cap` particles alive: the five entry points enqueued behind each other with no
+    synchronisation between them, then the first three again on another instance and with records of other sizes. Every result is the host's
+    restatement bit for bit: the forms share one table of kernel handles over three code objects, one launch plan and the scratch buffers, and
+    none of that may carry over from a call into the next. 4097: two tiles of the sort and the filter, the second of one row; 300: the
+    one-workgroup paths."""
+    bases = [0, 10_000, 20_000]
+    ctx, prog, fxs = pes.make(cap, 3, slot_bases=bases)
+    pes.step(ctx, fxs, 0, [37, 0, cap])
+    for f in (1, 2, 3):
+        pes.step(ctx, fxs, f, [0, 0, 0])
+    F, ID = POS_AGE_LIFE_VEL, pes.POS_AGE_ID
+    by_depth, by_distance = dict(key="depth", v=DIR), dict(key="distance", v=(1, 2, 3), descending=True)
+    full, few = fxs[2], fxs[0]
+    calls = [("plain effect", Export(F, 32, cap).run(full)),
+             ("program sorted, program scope", pes.run_sorted(Export(ID, 20, 3 * cap), prog, "program", **by_depth)),
+             ("filtered effect", run_filtered(Export(F, 32, cap), full, **HALF)),
+             ("program plain", Export(ID, 20, 3 * cap, n_offsets=4).run(prog)),
+             ("effect sorted", run_sorted(Export(F, 32, cap), full, **by_distance)),
+             ("program sorted, instance scope", pes.run_sorted(Export(ID, 20, 3 * cap, n_offsets=4), prog, "instance", **by_distance)),
+             ("plain effect again", Export(F, 256, cap).run(few)),
+             ("program sorted, program scope, again", pes.run_sorted(Export(ID, 72, 3 * cap), prog, "program", **by_distance)),
+             ("filtered effect again", run_filtered(Export(F, 48, cap), few, invert=True, **HALF))]
+    ctx.synchronize()
+    counts = [fx.alive_count() for fx in fxs]
+    assert counts == [37, 0, cap]
+    offsets = np.concatenate([[0], np.cumsum(counts)])
+    filtered_full, mask_full = expected_filtered(full, F, 32, **HALF)
+    filtered_few, mask_few = expected_filtered(few, F, 48, invert=True, **HALF)
+    assert 0 < mask_full.sum() < cap
+    want = [expected_records(full, F, 32),
+            pes.expected_program(fxs, ID, 20, "program", bases, **by_depth)[0],
+            filtered_full,
+            np.concatenate([expected_records(fx, ID, 20, slot_base=b) for fx, b in zip(fxs, bases)]),
+            expected_sorted(full, F, 32, **by_distance)[0],
+            pes.expected_program(fxs, ID, 20, "instance", bases, **by_distance)[0],
+            expected_records(few, F, 256),
+            pes.expected_program(fxs, ID, 72, "program", bases, **by_distance)[0],
+            filtered_few]
+    for (what, ex), rec in zip(calls, want):
+        assert_export(ex, rec, what, alive_rows=len(rec))
+        if ex.offsets is not None:
+            np.testing.assert_array_equal(ex.offsets.cpu().numpy().view(np.uint32), offsets, err_msg=what)
     ctx.close()
