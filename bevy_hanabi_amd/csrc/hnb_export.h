@@ -1,7 +1,7 @@
-// The packed exports (hnb_effect_export, hnb_program_export, their _sorted forms, hnb_effect_export_filtered; include/hanabi_amd.h "Packed output"),
-// shared by the kernels' translation units (hnb_export.hip, hnb_export_sort.hip, hnb_export_filter.hip: a code object each) and the runtime that loads
-// and launches them (hanabi_amd.hip): the kernels' argument blocks, the sort's pass and (instance, slot) arithmetic, the scratch layouts of the sort and
-// the filter, the kernels by name (ExportKernel) and the launches of a call (export_launch_plan). Plain C++ below the argument blocks: a host compiler
+// The packed exports (hnb_effect_export, hnb_program_export, their _sorted forms, hnb_effect_export_filtered, hnb_effect_export_filtered_sorted;
+// include/hanabi_amd.h "Packed output"), shared by the kernels' translation units (hnb_export.hip, hnb_export_sort.hip, hnb_export_filter.hip,
+// hnb_export_cull.hip: a code object each) and the runtime that loads and launches them (hanabi_amd.hip): the kernels' argument blocks, the sort's pass
+// and (instance, slot) arithmetic, the scratch layouts, the kernels by name (ExportKernel) and the launches of a call (export_launch_plan). Plain C++ below the argument blocks: a host compiler
 // takes it, so the tests check the layouts and the plan without a GPU.
 #pragma once
 #include <stdint.h>
@@ -190,39 +190,67 @@ HNB_SORT_KEY_FN ExportSortScratch export_sort_scratch_layout(uint32_t n_inst, ui
 }
 
 
+// ---- filtered, then sorted (hnb_effect_export_filtered_sorted; kernels: hnb_export_cull.hip, a fourth code object, and those of units 2 and 3) ----
+// The filter's compaction feeds the sort: k_export_cull_keys takes its rows from the filter's order[] and their count from its state word, the sort's
+// later kernels and the kRowsOrdered gather take the same count as the alive_count of a 32-byte row with HnbDeviceMeta's layout that lies where the
+// filter's state word does (f.state == (uint32_t*)s.meta; its other words are zeroed with the allocation and never written). Effects of one tile:
+// k_export_cull_tile does all of it in one workgroup.
+struct ExportCullArgs {
+    ExportFilterArgs f;             // as the filtered export binds it (meta: the effect's row), in the call's own scratch
+    ExportSortArgs s;               // as the sorted export binds it, except meta: the row that holds the kept count
+};
+
+// The scratch of an effect's filtered-then-sorted exports, one allocation: export_filter_scratch_layout, then (at sort_off, a 256-byte boundary)
+// export_sort_scratch_layout of one instance. 20 bytes per slot of capacity and, above 4096 slots, about 5.6 more for the digit tables and the mask.
+// sort.rows == 0: more than 0xFFFFFF00 slots, refused as the sorted export refuses them.
+struct ExportCullScratch { ExportFilterScratch filter; ExportSortScratch sort; uint64_t sort_off, total; };
+HNB_SORT_KEY_FN ExportCullScratch export_cull_scratch_layout(uint32_t capacity) {
+    ExportCullScratch l;
+    l.filter = export_filter_scratch_layout(capacity);
+    l.sort = export_sort_scratch_layout(1u, capacity, HNB_SORT_SCOPE_INSTANCE);
+    l.sort_off = (l.filter.total + 255u) & ~(uint64_t)255u;
+    l.total = l.sort_off + l.sort.total;
+    return l;
+}
+
+
 // ---- the host path of every form: which kernels there are, and which of them a call launches ----
-// The kernels of the three code objects, in the order of their units: the index of a kernel's handle in the context.
-enum ExportUnit : uint32_t { kUnitExport, kUnitExportSort, kUnitExportFilter, kExportUnits };
+// The kernels of the code objects, in the order of their units: the index of a kernel's handle in the context. kExpKernels: those of the first three
+// units; the fourth unit's follow it, and kExpKernelsAll sizes the handle arrays.
+enum ExportUnit : uint32_t { kUnitExport, kUnitExportSort, kUnitExportFilter, kUnitExportCull, kExportUnits };
 enum ExportKernel : uint32_t {
     kExpRows0, kExpRows1, kExpRows2, kExpRows3, kExpOffsets,                                                    // hnb_export.hip
     kExpSortRows0, kExpSortRows1, kExpSortRows2, kExpSortRows3, kExpSortTile, kExpSortKeys, kExpSortHist, kExpSortScatter,   // hnb_export_sort.hip: one effect,
     kExpSortRowsInst0, kExpSortRowsInst1, kExpSortRowsInst2, kExpSortRowsInst3, kExpSortTileInst, kExpSortKeysInst, kExpSortHistInst, kExpSortScatterInst,   // (tiles, instances),
     kExpSortRowsAll0, kExpSortRowsAll1, kExpSortRowsAll2, kExpSortRowsAll3, kExpSortFill, kExpSortHistAll, kExpSortScatterAll,   // all instances' rows as one space
     kExpFilterRows0, kExpFilterRows1, kExpFilterRows2, kExpFilterRows3, kExpFilterTile, kExpFilterMark, kExpFilterScan, kExpFilterCompact,   // hnb_export_filter.hip
-    kExpKernels
+    kExpKernels,
+    kExpCullTile = kExpKernels, kExpCullKeys,                                                                   // hnb_export_cull.hip
+    kExpKernelsAll
 };
 
-enum ExportForm : uint32_t { kExportPlain, kExportSorted, kExportFiltered };
+enum ExportForm : uint32_t { kExportPlain, kExportSorted, kExportFiltered, kExportFilteredSorted };
 // What a launch passes: an argument block by value (the sort's hist and scatter kernels take the pass behind it), or k_export_offsets' five words
-enum ExportArgBlock : uint32_t { kExportArgsRows, kExportArgsSort, kExportArgsSortPass, kExportArgsFilter, kExportArgsOffsets };
+enum ExportArgBlock : uint32_t { kExportArgsRows, kExportArgsSort, kExportArgsSortPass, kExportArgsFilter, kExportArgsOffsets, kExportArgsCull };
 struct ExportLaunch { uint32_t kernel, grid_x, grid_y, args, pass; };   // (workgroups of kExportBlock lanes)
 constexpr uint32_t kExportPlanMax = 12, kExportNoMemset = ~0u;
 struct ExportPlan {
     uint32_t n;                         // launches, in stream order
-    uint32_t memset_before;             // a multi-tile sort: bytes [zero_off, zero_off + zero_bytes) of the sort's scratch are zeroed in front of launch
-    uint64_t zero_off, zero_bytes;      //   `memset_before` (the state words and group sums); kExportNoMemset: nothing is
+    uint32_t memset_before;             // a multi-tile sort: bytes [zero_off, zero_off + zero_bytes) of the call's scratch are zeroed in front of launch
+    uint64_t zero_off, zero_bytes;      //   `memset_before` (the sort's state words and group sums); kExportNoMemset: nothing is
     ExportLaunch launch[kExportPlanMax];
 };
 
 // The gather of a form, by the LDS image of its records (export_variant)
 HNB_SORT_KEY_FN uint32_t export_rows_kernel(uint32_t form, bool program, uint32_t scope, uint32_t variant) {
-    const uint32_t first = form == kExportFiltered ? kExpFilterRows0 : form == kExportPlain ? kExpRows0 : !program ? kExpSortRows0 :
+    const uint32_t first = form == kExportFiltered ? kExpFilterRows0 : form == kExportPlain ? kExpRows0 : !program || form == kExportFilteredSorted ? kExpSortRows0 :
                            scope == HNB_SORT_SCOPE_PROGRAM ? kExpSortRowsAll0 : kExpSortRowsInst0;
     return first + variant;
 }
 
 // The launches of one export, in order. `program`: all n_inst instances of a program (plain or sorted in `scope`), else one effect (n_inst and scope
-// are not read). A sorted form's rows must fit (export_sort_scratch_layout(...).rows != 0). Decides; hanabi_amd.hip run_export_plan executes.
+// are not read). A sorted form's rows must fit (export_sort_scratch_layout(...).rows != 0). kExportFilteredSorted: one effect only. Decides;
+// hanabi_amd.hip run_export_plan executes.
 HNB_SORT_KEY_FN ExportPlan export_launch_plan(uint32_t form, bool program, uint32_t scope, uint32_t n_inst, uint32_t capacity, uint32_t stride_bytes) {
     ExportPlan pl = {};
     pl.memset_before = kExportNoMemset;
@@ -252,6 +280,20 @@ HNB_SORT_KEY_FN ExportPlan export_launch_plan(uint32_t form, bool program, uint3
             add(kExpFilterMark, tiles, 1u, kExportArgsFilter);
             add(kExpFilterScan, 1u, 1u, kExportArgsFilter);
             add(kExpFilterCompact, tiles, 1u, kExportArgsFilter);
+        }
+    } else if (form == kExportFilteredSorted) {
+        const ExportCullScratch l = export_cull_scratch_layout(capacity);
+        if (tiles <= 1u) add(kExpCullTile, 1u, 1u, kExportArgsCull);               // mark, compact into (key, slot) pairs and every pass by one workgroup
+        else {
+            add(kExpFilterMark, tiles, 1u, kExportArgsFilter);
+            add(kExpFilterScan, 1u, 1u, kExportArgsFilter);
+            add(kExpFilterCompact, tiles, 1u, kExportArgsFilter);
+            pl.memset_before = pl.n; pl.zero_off = l.sort_off + l.sort.state_off; pl.zero_bytes = l.sort.zero_bytes;
+            add(kExpCullKeys, tiles, 1u, kExportArgsCull);                         // the kept rows' keys, and pass 0's digit counts
+            for (uint32_t pass = 0; pass < kExportSortPasses; ++pass) {
+                if (pass) add(kExpSortHist, tiles, 1u, kExportArgsSortPass, pass);
+                add(kExpSortScatter, tiles, 1u, kExportArgsSortPass, pass);
+            }
         }
     }
     add(export_rows_kernel(form, program, scope, variant), (rows + tile_rows - 1u) / tile_rows, gy, kExportArgsRows);

@@ -31,7 +31,7 @@ ABI_SYMBOLS = [
     "hnb_simulate_steps", "hnb_effect_set_frames_ahead", "hnb_program_set_frames_ahead", "hnb_ctx_step_stats",
     "hnb_program_prepare_steps", "hnb_jit_precompile_steps",
     "hnb_effect_export", "hnb_program_export", "hnb_effect_export_sorted", "hnb_program_export_sorted",
-    "hnb_effect_export_filtered",
+    "hnb_effect_export_filtered", "hnb_effect_export_filtered_sorted",
 ]
 
 # hnb_ctx_set_option (include/hanabi_amd.h): name -> option id
@@ -279,6 +279,7 @@ def load_library():
         lib.hnb_effect_export_sorted.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.POINTER(ExportSort)]
         lib.hnb_program_export_sorted.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.POINTER(ExportSort), C.c_uint32, C.c_void_p]
         lib.hnb_effect_export_filtered.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.POINTER(ExportFilter)]
+        lib.hnb_effect_export_filtered_sorted.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.POINTER(ExportFilter), C.POINTER(ExportSort)]
         _lib = lib
     return _lib
 
@@ -637,6 +638,15 @@ class Effect:
         d = export_desc(fields, dst_ptr, stride, capacity_records, count_ptr)
         f = export_filter(kind, planes, sphere, attr, lo, hi, invert)
         _check(self._lib.hnb_effect_export_filtered(self._h, C.byref(d), C.byref(f)))
+
+    def export_filtered_sorted(self, fields, dst_ptr, stride, capacity_records, count_ptr=None, *, filter, sort):
+        """hnb_effect_export_filtered_sorted: the rows export_filtered() keeps, in the order export_sorted() gives them. `filter`: a dict of
+        export_filter's keywords (kind, planes, sphere, attr, lo, hi, invert); `sort`: a dict of export_sort's (key, v, attr, descending). A
+        destination of K records receives the first K kept rows of that order. count_ptr: [0] = records written, [1] = rows kept."""
+        d = export_desc(fields, dst_ptr, stride, capacity_records, count_ptr)
+        f = export_filter(**filter)
+        s = export_sort(**sort)
+        _check(self._lib.hnb_effect_export_filtered_sorted(self._h, C.byref(d), C.byref(f), C.byref(s)))
 
     def check(self):
         """hnb_effect_check: list permutation, alive bytes, age < lifetime, fault flag - on the device; a dict with "ok"."""

@@ -713,6 +713,39 @@ typedef struct HnbExportFilter {
 } HnbExportFilter;
 int hnb_effect_export_filtered(HnbEffect* fx, const HnbExportDesc* desc, const HnbExportFilter* filter);
 
+/* Filtered, then sorted export: the rows hnb_effect_export_filtered keeps, in the order hnb_effect_export_sorted gives them - the particles inside a
+ * frustum back to front, the K nearest inside a sphere - for a renderer that alpha-blends what it can see. The sort runs over the kept rows only.
+ * HnbExportDesc, HnbExportFilter and HnbExportSort are used unchanged.
+ * Rows
+ *   Exactly the rows hnb_effect_export_filtered keeps with `filter`: the same predicates, rounded operation by operation, the same NaN behaviour,
+ *   `invert` and ATTR_RANGE keys.
+ * Order
+ *   Among the kept rows, hnb_effect_export_sorted's with `sort`: the same key formulas, the f32 key transform and descending = ~k. Record r is the
+ *   kept particle with the r-th smallest key; kept rows with EQUAL keys stay in list order, ascending and descending alike.
+ * Counts and clamp
+ *   out_count[0] = the records written, min(kept, dst_capacity_records): the FIRST ones of that order, so a destination of K records gets the K
+ *   nearest (or oldest, ...) kept rows. out_count[1] = the rows kept. Records at and past the written count are not touched; padding dwords of
+ *   written records are zero.
+ * Two identities
+ *   With a filter that keeps every row, dst and out_count are byte for byte hnb_effect_export_sorted's. With a key that is equal for every kept
+ *   row, they are byte for byte hnb_effect_export_filtered's.
+ * Everything the other exports promise holds: enqueued on the simulation stream behind the frames enqueued so far, no host synchronisation and no
+ *   readback on the steady path; the alive count, the list column and the ring head are read from the HnbDeviceMeta row on the device, and so is
+ *   the kept count; every grid is sized from the capacity; no workgroup waits for another. Stale AGE is materialised first when AGE is a record
+ *   field, the sort key or the ATTR_RANGE source. The simulation is only read: lists, planes and every later frame are bit for bit what they would
+ *   be without the call, and a following hnb_effect_export is in list order.
+ * Errors: HNB_ERR_INVALID_ARG (with hnb_last_error text; nothing is enqueued) for a NULL argument and for everything hnb_effect_export_filtered or
+ *   hnb_effect_export_sorted rejects (an effect of more than 0xFFFFFF00 slots among it).
+ * Scratch: owned by the library, per effect, one allocation of its own: 20 bytes per slot of capacity (the kept rows' slots and two (key, slot)
+ *   buffers) plus, for capacities above 4096, about 5.6 bytes per slot of digit tables, mask and tile words. Allocated by the effect's FIRST such
+ *   export - that one call may synchronise the device once for the allocation - and freed with the effect. Exports of one effect reuse it in stream
+ *   order. It is neither the scratch of hnb_effect_export_filtered nor that of hnb_effect_export_sorted: the three calls may be interleaved on one
+ *   effect.
+ * The kernels: those of the filtered and of the sorted export, unchanged, and two that join them (the keys of the kept rows; for effects of at most
+ *   4096 slots the whole cull and sort by one workgroup), which live in a fourth code object that the library carries and loads on first use;
+ *   HNB_ERR_HIP if it cannot be loaded. */
+int hnb_effect_export_filtered_sorted(HnbEffect* fx, const HnbExportDesc* desc, const HnbExportFilter* filter, const HnbExportSort* sort);
+
 /* Readback (synchronising; reporting / parity only, never on the frame path). */
 int hnb_effect_metadata(HnbEffect* fx, HnbEffectMetadata* out);
 int hnb_effect_alive_count(HnbEffect* fx, uint32_t* out);
