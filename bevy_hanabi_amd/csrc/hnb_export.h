@@ -1,8 +1,9 @@
-// The packed exports (hnb_effect_export, hnb_program_export, their _sorted forms, hnb_effect_export_filtered, hnb_effect_export_filtered_sorted;
-// include/hanabi_amd.h "Packed output"), shared by the kernels' translation units (hnb_export.hip, hnb_export_sort.hip, hnb_export_filter.hip,
-// hnb_export_cull.hip: a code object each) and the runtime that loads and launches them (hanabi_amd.hip): the kernels' argument blocks, the sort's pass
-// and (instance, slot) arithmetic, the scratch layouts, the kernels by name (ExportKernel) and the launches of a call (export_launch_plan). Plain C++ below the argument blocks: a host compiler
-// takes it, so the tests check the layouts and the plan without a GPU.
+// The packed exports (hnb_effect_export, hnb_program_export, their _sorted forms, hnb_effect_export_filtered, hnb_effect_export_filtered_sorted,
+// hnb_program_export_filtered; include/hanabi_amd.h "Packed output"), shared by the kernels' translation units (hnb_export.hip, hnb_export_sort.hip,
+// hnb_export_filter.hip, hnb_export_cull.hip, hnb_export_filter_prog.hip: a code object each) and the runtime that loads and launches them
+// (hanabi_amd.hip): the kernels' argument blocks, the sort's pass and (instance, slot) arithmetic, the scratch layouts, the kernels by name
+// (ExportKernel) and the launches of a call (export_launch_plan). Plain C++ below the argument blocks: a host compiler takes it, so the tests check
+// the layouts and the plan without a GPU.
 #pragma once
 #include <stdint.h>
 
@@ -214,10 +215,60 @@ HNB_SORT_KEY_FN ExportCullScratch export_cull_scratch_layout(uint32_t capacity) 
 }
 
 
+// ---- filtered export, program form (hnb_program_export_filtered; kernels: hnb_export_filter_prog.hip, a fifth code object, and k_export_offsets) ----
+// The filtered export's compaction once per instance, the instance being blockIdx.y: every scratch section of the effect form exists per instance,
+// and the state word of instance k is word 0 of kept[k], a 32-byte row with HnbDeviceMeta's layout whose other words are zeroed with the allocation
+// and never written. k_export_offsets, bound to those rows, scans the kept counts; the kRowsFilteredInstance gather takes count and first record
+// from the same rows and from offsets[]. No workgroup waits for another.
+struct ExportFilterRow {            // what of an HnbExportFilter may differ between the instances of one call: a device row per instance
+    float P[HNB_FILTER_MAX_PLANES][4];
+    uint32_t n_planes, invert, lo_bits, hi_bits;
+    uint32_t pad[4];
+};
+static_assert(sizeof(ExportFilterRow) == 128, "a filter row is 128 bytes");
+
+struct ExportFilterProgArgs {
+    ExportFilterArgs f;             // slab, meta: the program's tables [n_inst]; order, mask, tile_count, tile_offset: instance 0's section, instance k's lies k
+                                    //   sections behind it; state: kept[0]; n_planes, invert, lo_bits, hi_bits, P: the one filter of a call that shares it
+    const ExportFilterRow* filters; // [n_inst] a filter per instance; NULL: every instance takes f's
+    uint32_t n_inst;
+    uint32_t order_pitch;           // slots between two instances' sections of order[]
+};
+
+// The scratch of a program's filtered exports, one allocation; every section starts on a 256-byte boundary. Per instance: 4 bytes per slot of
+// capacity (order), per tile of 4096 slots 512 bytes of mask and two words, a 32-byte kept row and a 128-byte filter row.
+struct ExportFilterProgScratch {
+    uint32_t n_inst, tiles, pitch;  // tiles of ONE instance; pitch: slots of one instance's section of order[]
+    uint64_t order_off, order_bytes, mask_off, mask_bytes, count_off, count_bytes, offset_off, offset_bytes, kept_off, kept_bytes, filter_off, filter_bytes, total;
+};
+HNB_SORT_KEY_FN ExportFilterProgScratch export_filter_prog_scratch_layout(uint32_t n_inst, uint32_t capacity) {
+    ExportFilterProgScratch l;
+    const uint64_t n = n_inst, align = 255u;
+    l.n_inst = n_inst;
+    l.tiles = (uint32_t)(((uint64_t)capacity + kExportFilterTile - 1u) / kExportFilterTile);
+    l.pitch = capacity;
+    l.order_off = 0;
+    l.order_bytes = n * l.pitch * 4u;
+    l.mask_off = (l.order_off + l.order_bytes + align) & ~align;
+    l.mask_bytes = n * l.tiles * kExportFilterTileWords * 8u;
+    l.count_off = (l.mask_off + l.mask_bytes + align) & ~align;
+    l.count_bytes = n * l.tiles * 4u;
+    l.offset_off = (l.count_off + l.count_bytes + align) & ~align;
+    l.offset_bytes = n * l.tiles * 4u;
+    l.kept_off = (l.offset_off + l.offset_bytes + align) & ~align;
+    l.kept_bytes = n * sizeof(HnbDeviceMeta);
+    l.filter_off = (l.kept_off + l.kept_bytes + align) & ~align;
+    l.filter_bytes = n * sizeof(ExportFilterRow);
+    l.total = (l.filter_off + l.filter_bytes + align) & ~align;
+    return l;
+}
+
+
 // ---- the host path of every form: which kernels there are, and which of them a call launches ----
 // The kernels of the code objects, in the order of their units: the index of a kernel's handle in the context. kExpKernels: those of the first three
-// units; the fourth unit's follow it, and kExpKernelsAll sizes the handle arrays.
-enum ExportUnit : uint32_t { kUnitExport, kUnitExportSort, kUnitExportFilter, kUnitExportCull, kExportUnits };
+// units; the fourth unit's follow it up to kExpKernelsAll, the fifth unit's follow those, and kExpKernelCount sizes the handle arrays (kExportUnitCount
+// the module array): a later unit is numbered behind the earlier ones, whose values stay.
+enum ExportUnit : uint32_t { kUnitExport, kUnitExportSort, kUnitExportFilter, kUnitExportCull, kExportUnits, kUnitExportFilterProg = kExportUnits, kExportUnitCount };
 enum ExportKernel : uint32_t {
     kExpRows0, kExpRows1, kExpRows2, kExpRows3, kExpOffsets,                                                    // hnb_export.hip
     kExpSortRows0, kExpSortRows1, kExpSortRows2, kExpSortRows3, kExpSortTile, kExpSortKeys, kExpSortHist, kExpSortScatter,   // hnb_export_sort.hip: one effect,
@@ -226,12 +277,15 @@ enum ExportKernel : uint32_t {
     kExpFilterRows0, kExpFilterRows1, kExpFilterRows2, kExpFilterRows3, kExpFilterTile, kExpFilterMark, kExpFilterScan, kExpFilterCompact,   // hnb_export_filter.hip
     kExpKernels,
     kExpCullTile = kExpKernels, kExpCullKeys,                                                                   // hnb_export_cull.hip
-    kExpKernelsAll
+    kExpKernelsAll,
+    kExpFilterRowsInst0 = kExpKernelsAll, kExpFilterRowsInst1, kExpFilterRowsInst2, kExpFilterRowsInst3,        // hnb_export_filter_prog.hip: (tiles, instances)
+    kExpFilterTileInst, kExpFilterMarkInst, kExpFilterScanInst, kExpFilterCompactInst,
+    kExpKernelCount
 };
 
 enum ExportForm : uint32_t { kExportPlain, kExportSorted, kExportFiltered, kExportFilteredSorted };
 // What a launch passes: an argument block by value (the sort's hist and scatter kernels take the pass behind it), or k_export_offsets' five words
-enum ExportArgBlock : uint32_t { kExportArgsRows, kExportArgsSort, kExportArgsSortPass, kExportArgsFilter, kExportArgsOffsets, kExportArgsCull };
+enum ExportArgBlock : uint32_t { kExportArgsRows, kExportArgsSort, kExportArgsSortPass, kExportArgsFilter, kExportArgsOffsets, kExportArgsCull, kExportArgsFilterProg };
 struct ExportLaunch { uint32_t kernel, grid_x, grid_y, args, pass; };   // (workgroups of kExportBlock lanes)
 constexpr uint32_t kExportPlanMax = 12, kExportNoMemset = ~0u;
 struct ExportPlan {
@@ -243,14 +297,15 @@ struct ExportPlan {
 
 // The gather of a form, by the LDS image of its records (export_variant)
 HNB_SORT_KEY_FN uint32_t export_rows_kernel(uint32_t form, bool program, uint32_t scope, uint32_t variant) {
-    const uint32_t first = form == kExportFiltered ? kExpFilterRows0 : form == kExportPlain ? kExpRows0 : !program || form == kExportFilteredSorted ? kExpSortRows0 :
+    const uint32_t first = form == kExportFiltered ? (program ? kExpFilterRowsInst0 : kExpFilterRows0) : form == kExportPlain ? kExpRows0 : !program || form == kExportFilteredSorted ? kExpSortRows0 :
                            scope == HNB_SORT_SCOPE_PROGRAM ? kExpSortRowsAll0 : kExpSortRowsInst0;
     return first + variant;
 }
 
 // The launches of one export, in order. `program`: all n_inst instances of a program (plain or sorted in `scope`), else one effect (n_inst and scope
-// are not read). A sorted form's rows must fit (export_sort_scratch_layout(...).rows != 0). kExportFilteredSorted: one effect only. Decides;
-// hanabi_amd.hip run_export_plan executes.
+// are not read). A sorted form's rows must fit (export_sort_scratch_layout(...).rows != 0). kExportFilteredSorted: one effect only. The filtered
+// program form scans KEPT counts, so its k_export_offsets runs behind the instances' compaction counts, not in front. Decides; hanabi_amd.hip
+// run_export_plan executes.
 HNB_SORT_KEY_FN ExportPlan export_launch_plan(uint32_t form, bool program, uint32_t scope, uint32_t n_inst, uint32_t capacity, uint32_t stride_bytes) {
     ExportPlan pl = {};
     pl.memset_before = kExportNoMemset;
@@ -260,7 +315,7 @@ HNB_SORT_KEY_FN ExportPlan export_launch_plan(uint32_t form, bool program, uint3
     const uint32_t rows = all ? n * capacity : capacity, gy = all ? 1u : n;        // of the gather's row space, and how many of them
     const uint32_t variant = export_variant(stride_bytes), tile_rows = export_tile_rows(variant);
     const auto add = [&pl](uint32_t kernel, uint32_t gx, uint32_t gy, uint32_t args, uint32_t pass = 0u) { pl.launch[pl.n++] = ExportLaunch{kernel, gx, gy, args, pass}; };
-    if (program) add(kExpOffsets, 1u, 1u, kExportArgsOffsets);
+    if (program && form != kExportFiltered) add(kExpOffsets, 1u, 1u, kExportArgsOffsets);
     if (form == kExportSorted) {
         const ExportSortScratch l = export_sort_scratch_layout(n, capacity, all ? HNB_SORT_SCOPE_PROGRAM : HNB_SORT_SCOPE_INSTANCE);
         const uint32_t tile = program ? kExpSortTileInst : kExpSortTile, keys = all ? kExpSortFill : program ? kExpSortKeysInst : kExpSortKeys;
@@ -274,6 +329,14 @@ HNB_SORT_KEY_FN ExportPlan export_launch_plan(uint32_t form, bool program, uint3
                 add(scatter, l.tiles, gy, kExportArgsSortPass, pass);
             }
         }
+    } else if (form == kExportFiltered && program) {
+        if (tiles <= 1u) add(kExpFilterTileInst, 1u, n, kExportArgsFilterProg);    // every instance's mark, count and compact by one workgroup
+        else {
+            add(kExpFilterMarkInst, tiles, n, kExportArgsFilterProg);
+            add(kExpFilterScanInst, 1u, n, kExportArgsFilterProg);
+        }
+        add(kExpOffsets, 1u, 1u, kExportArgsOffsets);                              // over the kept counts
+        if (tiles > 1u) add(kExpFilterCompactInst, tiles, n, kExportArgsFilterProg);
     } else if (form == kExportFiltered) {
         if (tiles <= 1u) add(kExpFilterTile, 1u, 1u, kExportArgsFilter);           // mark, count and compact by one workgroup
         else {

@@ -15,7 +15,7 @@
 // waits for another.
 #include <hip/hip_runtime.h>
 
-#include "hnb_export_filter.hip.h"   // the rows a filter kernel reads, the predicate of a slot, a tile's mask and its prefix
+#include "hnb_export_filter.hip.h"   // the rows a filter kernel reads, the predicate of a slot, a tile's mask, its prefix and its compaction
 
 #pragma clang fp contract(off)   // the predicates are rounded operation by operation (the unit is also built with -ffp-contract=off)
 
@@ -23,27 +23,7 @@ using namespace hnb;
 
 namespace {
 
-constexpr uint32_t kBlock = kExportBlock;
-constexpr uint32_t kWaves = kFilterWaves;
-constexpr uint32_t kRounds = kFilterRounds;
 constexpr uint32_t kWords = kFilterWords;
-
-// The kept rows of tile j, by its mask in s_word and the prefix in s_pref, to order[first + rank]. A row is read from the list only when its bit is
-// set; a bit is set only for rows below the count (mark_tile), and the test is made again here: nothing outside the list is read and nothing outside
-// order[0, capacity) is written whatever the scratch holds.
-__device__ __forceinline__ void compact_tile(const ExportFilterArgs& a, const FilterSource& s, uint32_t j, const uint64_t* s_word, const uint32_t* s_pref, uint32_t first, uint32_t tid) {
-    const uint32_t lane = tid & 63u, wave = tid >> 6;
-    for (uint32_t r = 0; r < kRounds; ++r) {
-        const uint32_t rbase = j * kExportFilterTile + r * kBlock;
-        if (rbase >= s.n) break;
-        const uint32_t w = r * kWaves + wave, i = rbase + tid;
-        const uint64_t word = s_word[w];
-        if (((word >> lane) & 1ull) && i < s.n) {
-            const uint32_t at = first + s_pref[w] + (uint32_t)__popcll(word & ((1ull << lane) - 1ull));
-            if (at < a.capacity) a.order[at] = s.list[ring_index(s.head, i, a.capacity)];
-        }
-    }
-}
 
 }  // namespace
 

@@ -1,6 +1,6 @@
 // The gather of the packed export (hnb_export.hip: k_export_rows_*, slots from the alive list; hnb_export_sort.hip: k_export_sort_rows_*, slots
 // from the order a sorted export produced; k_export_sort_rows_inst_* / _all_*: the two scopes of the sorted program export; hnb_export_filter.hip:
-// k_export_filter_rows_*, the slots a filtered export kept). One body; the instantiations by where a row's slot comes from.
+// k_export_filter_rows_*, the slots a filtered export kept; hnb_export_filter_prog.hip: k_export_filter_rows_inst_*, the same per instance). One body; the instantiations by where a row's slot comes from.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -41,7 +41,9 @@ __device__ __forceinline__ void store_field(uint32_t* rec, const ExportFieldArg 
 //   kRowsOrderedProgram    one order over all instances: order[r] names (instance, slot); the rows are those of the concatenated space, the
 //                          instance's slab and slot base are taken per lane
 //   kRowsFiltered          order[r], the slots a filtered export kept (one buffer); the rows are order_state[0], the kept total, not alive_count
-constexpr uint32_t kRowsList = 0, kRowsOrdered = 1, kRowsOrderedInstance = 2, kRowsOrderedProgram = 3, kRowsFiltered = 4;
+//   kRowsFilteredInstance  instance blockIdx.y's section of the filtered program export's order[] (order_pitch slots each); meta[] are the kept rows:
+//                          alive_count is the instance's kept count, their other words are zero (the list they would name is never read)
+constexpr uint32_t kRowsList = 0, kRowsOrdered = 1, kRowsOrderedInstance = 2, kRowsOrderedProgram = 3, kRowsFiltered = 4, kRowsFilteredInstance = 5;
 template <uint32_t LDS_DWORDS, uint32_t ORDER>
 __device__ __forceinline__ void export_rows(const ExportArgs& a) {
     __shared__ __attribute__((aligned(16))) uint32_t image[LDS_DWORDS];
@@ -56,6 +58,7 @@ __device__ __forceinline__ void export_rows(const ExportArgs& a) {
         const uint32_t kept = a.order_state[0];
         n = kept < a.capacity ? kept : a.capacity;
     }
+    if constexpr (ORDER == kRowsFilteredInstance) n = n < a.capacity ? n : a.capacity;   // (a kept count; the compaction bounded it the same way)
     const uint32_t row0 = blockIdx.x * a.tile_rows;
     if (a.out_count && blockIdx.x == 0u && tid == 0u) {                           // (effect form only)
         a.out_count[0] = (uint64_t)n < a.dst_capacity ? n : (uint32_t)a.dst_capacity;
@@ -86,6 +89,9 @@ __device__ __forceinline__ void export_rows(const ExportArgs& a) {
         } else if constexpr (ORDER == kRowsFiltered) {
             slot = a.order[row0 + tid];
             if (slot >= a.capacity) slot = a.capacity - 1u;                       // (the compaction wrote list entries; nothing is read outside the planes whatever the buffer holds)
+        } else if constexpr (ORDER == kRowsFilteredInstance) {
+            slot = a.order[(size_t)k * a.order_pitch + row0 + tid];
+            if (slot >= a.capacity) slot = a.capacity - 1u;                       // (as above)
         } else slot = list[ring_index(head, row0 + tid, a.capacity)];
         const uint32_t id = (a.slot_bases ? a.slot_bases[ki] : a.slot_base) + slot;
         uint32_t* rec = image + tid * sdw;

@@ -31,7 +31,7 @@ ABI_SYMBOLS = [
     "hnb_simulate_steps", "hnb_effect_set_frames_ahead", "hnb_program_set_frames_ahead", "hnb_ctx_step_stats",
     "hnb_program_prepare_steps", "hnb_jit_precompile_steps",
     "hnb_effect_export", "hnb_program_export", "hnb_effect_export_sorted", "hnb_program_export_sorted",
-    "hnb_effect_export_filtered", "hnb_effect_export_filtered_sorted",
+    "hnb_effect_export_filtered", "hnb_effect_export_filtered_sorted", "hnb_program_export_filtered",
 ]
 
 # hnb_ctx_set_option (include/hanabi_amd.h): name -> option id
@@ -280,6 +280,7 @@ def load_library():
         lib.hnb_program_export_sorted.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.POINTER(ExportSort), C.c_uint32, C.c_void_p]
         lib.hnb_effect_export_filtered.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.POINTER(ExportFilter)]
         lib.hnb_effect_export_filtered_sorted.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.POINTER(ExportFilter), C.POINTER(ExportSort)]
+        lib.hnb_program_export_filtered.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.POINTER(ExportFilter), C.c_uint32, C.c_void_p]
         _lib = lib
     return _lib
 
@@ -520,6 +521,15 @@ class Program:
         s = export_sort(key, v, attr, descending)
         sc = SORT_SCOPES[scope] if isinstance(scope, str) else int(scope)
         _check(self._lib.hnb_program_export_sorted(self._h, C.byref(d), C.byref(s), sc, C.c_void_p(int(offsets_ptr)) if offsets_ptr else None))
+
+    def export_filtered(self, fields, dst_ptr, stride, capacity_records, count_ptr=None, offsets_ptr=None, *, filter):
+        """hnb_program_export_filtered: the records of export() for the rows a predicate keeps, every instance's segment in list order. `filter`:
+        one filter for all instances or a list with one per instance (same kind and attr); each a dict of export_filter's keywords (kind, planes,
+        sphere, attr, lo, hi, invert) or an ExportFilter. offsets_ptr / count_ptr as in export(), over the kept rows. Asynchronous."""
+        d = export_desc(fields, dst_ptr, stride, capacity_records, count_ptr)
+        fs = filter if isinstance(filter, (list, tuple)) else [filter]
+        arr = (ExportFilter * max(len(fs), 1))(*[f if isinstance(f, ExportFilter) else export_filter(**f) for f in fs])
+        _check(self._lib.hnb_program_export_filtered(self._h, C.byref(d), arr, len(fs), C.c_void_p(int(offsets_ptr)) if offsets_ptr else None))
 
     def kernel_info(self):
         """Which kernels run this program: 'init=jit|interp|none update=aot-stream:<name>|jit-stream|jit-generic|interp-*'."""

@@ -746,6 +746,41 @@ int hnb_effect_export_filtered(HnbEffect* fx, const HnbExportDesc* desc, const H
  *   HNB_ERR_HIP if it cannot be loaded. */
 int hnb_effect_export_filtered_sorted(HnbEffect* fx, const HnbExportDesc* desc, const HnbExportFilter* filter, const HnbExportSort* sort);
 
+/* Filtered export, program form: what a camera sees of a batch - hnb_program_export with hnb_effect_export_filtered's predicate in front of every
+ * instance, in one call. HnbExportDesc and HnbExportFilter are used unchanged.
+ * Records
+ *   The layout of hnb_program_export: instances back to back in instance order (hnb_effect_index). Instance k's segment is byte for byte what
+ *   hnb_effect_export_filtered(effect k, the filter of k) writes: the rows the predicate keeps, in list order, ring lists read through their head,
+ *   HNB_ATTR_ID as slot_base + slot, padding dwords zero.
+ * Filters
+ *   `filters` is a HOST array. n_filters == 1: every instance takes filters[0]; it travels by value with the launches, nothing is uploaded.
+ *   n_filters == the program's instance count: instance k takes filters[k] - no transform is applied (above), so instances simulated in local
+ *   space need a frustum each. All filters of a call have the same `kind` and `attr` (one source plane); n_planes, P, lo_bits, hi_bits and invert
+ *   may differ. Per-instance filters are packed into a pinned staging buffer the program owns and copied to the device with one asynchronous copy
+ *   on the simulation stream; `filters` itself may be reused as soon as the call returns. The NEXT call with per-instance filters waits on the host
+ *   until that copy has left the staging buffer before it rewrites it: the only wait of the steady path, and none with a shared filter.
+ * Counts and clamp
+ *   out_offsets[k] = the first record of instance k - the exclusive scan of the KEPT counts, computed on the device -, out_offsets[n_instances] =
+ *   the kept total. out_count[0] = min(kept total, dst_capacity_records), out_count[1] = the kept total. The clamp is global, as in
+ *   hnb_program_export: an instance that is cut keeps its first kept rows; records at and past the written count are not touched.
+ * One identity
+ *   With filters that keep every row, dst, out_offsets and out_count are byte for byte hnb_program_export's.
+ * Everything the other exports promise holds: enqueued on the simulation stream behind the frames enqueued so far, no readback and (but for the
+ *   staging wait above) no host synchronisation on the steady path; alive counts, list columns, ring heads and kept counts are read on the device;
+ *   every grid is sized from the capacity and the instance count; no workgroup waits for another. Stale AGE is materialised for all instances first
+ *   when AGE is a record field or the ATTR_RANGE source. Instances that are not simulated export their frozen state. The simulation is only read.
+ * Errors: HNB_ERR_INVALID_ARG (with hnb_last_error text; nothing is enqueued) for everything hnb_program_export rejects, for everything
+ *   hnb_effect_export_filtered rejects in any filters[i] (the text names i), for `filters` NULL, n_filters neither 1 nor the instance count, and
+ *   filters that differ in kind or attr.
+ * Scratch: owned by the library, per program, one allocation of its own - neither the sorted program export's nor any effect's: per instance 4
+ *   bytes per slot of capacity, 520 bytes per 4096 slots and 160 bytes of kept count and filter row. Allocated by the program's FIRST such export,
+ *   allocated again - behind one synchronisation of the stream - when the program has gained instances since, freed with the program.
+ * The kernels (the filtered export's mark, scan and compact with the instance as a second grid dimension, one workgroup per instance at up to 4096
+ *   slots, hnb_program_export's scan of the counts, and the gather) live in a fifth code object that the library carries and loads on first use;
+ *   HNB_ERR_HIP if it cannot be loaded. */
+int hnb_program_export_filtered(HnbProgram* prog, const HnbExportDesc* desc, const HnbExportFilter* filters, uint32_t n_filters,
+                                uint32_t* out_offsets /* device [n_instances + 1], may be NULL */);
+
 /* Readback (synchronising; reporting / parity only, never on the frame path). */
 int hnb_effect_metadata(HnbEffect* fx, HnbEffectMetadata* out);
 int hnb_effect_alive_count(HnbEffect* fx, uint32_t* out);
