@@ -32,6 +32,7 @@ ABI_SYMBOLS = [
     "hnb_program_prepare_steps", "hnb_jit_precompile_steps",
     "hnb_effect_export", "hnb_program_export", "hnb_effect_export_sorted", "hnb_program_export_sorted",
     "hnb_effect_export_filtered", "hnb_effect_export_filtered_sorted", "hnb_program_export_filtered",
+    "hnb_effect_bounds", "hnb_program_bounds",
 ]
 
 # hnb_ctx_set_option (include/hanabi_amd.h): name -> option id
@@ -211,6 +212,26 @@ def export_filter(kind, planes=(), sphere=None, attr=0, lo=0, hi=0, invert=False
     return f
 
 
+class Bounds(C.Structure):
+    """HnbBounds (hnb_effect_bounds / hnb_program_bounds): one 48-byte record as the device writes it."""
+    _fields_ = [("lo", C.c_float * 4), ("hi", C.c_float * 4), ("alive", C.c_uint32), ("nan", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class BoundsDesc(C.Structure):
+    """HnbBoundsDesc: the attribute whose bounds are taken and the device buffer of the records."""
+    _fields_ = [("struct_size", C.c_uint32), ("attr", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32), ("dst", C.c_void_p),
+                ("dst_capacity_records", C.c_uint64)]
+
+
+def bounds_desc(attr, dst_ptr, capacity_records):
+    d = BoundsDesc()
+    d.struct_size = C.sizeof(BoundsDesc)
+    d.attr = int(attr)
+    d.dst = int(dst_ptr) if dst_ptr else None
+    d.dst_capacity_records = int(capacity_records)
+    return d
+
+
 _lib = None
 
 
@@ -281,6 +302,8 @@ def load_library():
         lib.hnb_effect_export_filtered.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.POINTER(ExportFilter)]
         lib.hnb_effect_export_filtered_sorted.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.POINTER(ExportFilter), C.POINTER(ExportSort)]
         lib.hnb_program_export_filtered.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.POINTER(ExportFilter), C.c_uint32, C.c_void_p]
+        lib.hnb_effect_bounds.argtypes = [C.c_void_p, C.POINTER(BoundsDesc)]
+        lib.hnb_program_bounds.argtypes = [C.c_void_p, C.POINTER(BoundsDesc)]
         _lib = lib
     return _lib
 
@@ -531,6 +554,13 @@ class Program:
         arr = (ExportFilter * max(len(fs), 1))(*[f if isinstance(f, ExportFilter) else export_filter(**f) for f in fs])
         _check(self._lib.hnb_program_export_filtered(self._h, C.byref(d), arr, len(fs), C.c_void_p(int(offsets_ptr)) if offsets_ptr else None))
 
+    def bounds(self, attr, dst_ptr, capacity_records):
+        """hnb_program_bounds: a Bounds record per instance at the device address dst_ptr (16-byte aligned), in instance order, and their union behind
+        them: capacity_records >= n_instances + 1. Per component of the f32 attribute `attr` the smallest and the largest stored value among the
+        alive particles, in the order of the sorted export's key. Asynchronous: enqueued on the simulation stream, nothing is read back."""
+        d = bounds_desc(attr, dst_ptr, capacity_records)
+        _check(self._lib.hnb_program_bounds(self._h, C.byref(d)))
+
     def kernel_info(self):
         """Which kernels run this program: 'init=jit|interp|none update=aot-stream:<name>|jit-stream|jit-generic|interp-*'."""
         buf = C.create_string_buffer(4096)
@@ -657,6 +687,13 @@ class Effect:
         f = export_filter(**filter)
         s = export_sort(**sort)
         _check(self._lib.hnb_effect_export_filtered_sorted(self._h, C.byref(d), C.byref(f), C.byref(s)))
+
+    def bounds(self, attr, dst_ptr, capacity_records=1):
+        """hnb_effect_bounds: one Bounds record at the device address dst_ptr (16-byte aligned) - per component of the f32 attribute `attr` the
+        smallest and the largest stored value among the alive particles (POSITION: the effect's axis-aligned box), the alive particles and those
+        with a NaN. Asynchronous: enqueued on the simulation stream, nothing is read back."""
+        d = bounds_desc(attr, dst_ptr, capacity_records)
+        _check(self._lib.hnb_effect_bounds(self._h, C.byref(d)))
 
     def check(self):
         """hnb_effect_check: list permutation, alive bytes, age < lifetime, fault flag - on the device; a dict with "ok"."""

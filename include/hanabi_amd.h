@@ -781,6 +781,62 @@ int hnb_effect_export_filtered_sorted(HnbEffect* fx, const HnbExportDesc* desc, 
 int hnb_program_export_filtered(HnbProgram* prog, const HnbExportDesc* desc, const HnbExportFilter* filters, uint32_t n_filters,
                                 uint32_t* out_offsets /* device [n_instances + 1], may be NULL */);
 
+/* ---- Bounds --------------------------------------------------------------------------------------------------------------------
+ * Where an effect is as a whole: per component of ONE f32 attribute, the smallest and the largest value among the alive particles - with
+ * HNB_ATTR_POSITION the axis-aligned box of the effect. The reference computes no particle bounds (its users set an Aabb by hand or switch frustum
+ * culling off); here the record is one more device-resident output with the exports' contract: what a host bases hnb_effect_set_simulated, camera
+ * framing, a level of detail or the skipping of a whole instance on, and what says whether anything escaped to 1e30.
+ * Order
+ *   The sorted export's ascending f32 key: k = b ^ ((b >> 31) ? 0xFFFFFFFF : 0x80000000) of the stored bits b. lo[c] is the stored value with the
+ *   smallest key among the alive particles whose component c is not a NaN, hi[c] the one with the largest. So -0 < +0, and -inf / +inf take part:
+ *   an escaped particle makes the box infinite, the conservative answer. A bit pattern, not an approximation: min / max in this order do not depend
+ *   on the order the particles are visited in, and a restatement in another language reproduces the record exactly.
+ * NaN
+ *   A NaN component is skipped for that component only (the particle's other components take part); `nan` counts PARTICLES with a NaN in at least
+ *   one component, not components.
+ * Empty
+ *   A component no particle contributed to - nothing alive, or a NaN in it in every alive particle - is lo = +inf (0x7F800000), hi = -inf
+ *   (0xFF800000). Components at and past the attribute's count are bits 0 in lo and hi.
+ * Values
+ *   As stored: no transform is applied, nothing is padded by SIZE (a caller that wants a padded box asks for HNB_ATTR_SIZE's range in a second call).
+ * Program form
+ *   Record k is instance k (hnb_effect_index), byte for byte what hnb_effect_bounds writes for effect k. Record n_instances is the union: lo and hi
+ *   folded by the same rule over the instance records, alive and nan summed (modulo 2^32). Instances simulated in local space each have a box in
+ *   their own space: their union means something only to a caller who knows they share one. Instances that are not simulated report their frozen state.
+ * Contract
+ *   The exports': enqueued on the simulation stream behind the frames enqueued so far, no host synchronisation and no readback on the steady path
+ *   (the FIRST call of an effect / a program above 4096 slots allocates its scratch and may synchronise once); alive counts are read from
+ *   HnbDeviceMeta on the device; every grid is sized from the capacity and the instance count; no workgroup waits for another; nothing is zeroed per
+ *   call and there are no atomics. The alive list is not read: the walk is over the slots and their alive bytes, so its cost does not depend on what
+ *   churn has done to the list. Stale AGE is materialised first when `attr` is HNB_ATTR_AGE and stale_attr_mask has it. The simulation is only read:
+ *   lists, planes and every later frame are bit for bit what they would be without the call. Bytes behind the last record are not touched.
+ * Errors: HNB_ERR_INVALID_ARG (with hnb_last_error text; nothing is enqueued) for a NULL argument, another struct_size, flags or reserved not 0, dst
+ *   NULL or not 16-byte aligned, dst_capacity_records below 1 (effect form) or below n_instances + 1 (program form), an attribute the layout lacks,
+ *   one that is not f32, HNB_ATTR_ID / HNB_ATTR_PARTICLE_COUNTER (which have no plane), a program without instances or with more than 65535.
+ * Scratch: owned by the library, one allocation per effect and one per program, apart from every export's: 64 bytes per 4096 slots and instance,
+ *   none at all up to 4096 slots. Allocated by the first call, allocated again - behind one synchronisation of the stream - when the program has
+ *   gained instances since, freed with its owner.
+ * The kernels (one workgroup per 4096 slots and instance, a fold of an instance's tiles, the union; one workgroup per instance and no scratch up to
+ *   4096 slots: one launch for an effect, two for a program, above that two and three) live in a sixth code object that the library carries and
+ *   loads on first use; HNB_ERR_HIP if it cannot be loaded. */
+typedef struct HnbBounds {            /* 48 bytes */
+    float    lo[4];                   /* per component c < ncomp: the smallest non-NaN value; components >= ncomp: bits 0 */
+    float    hi[4];                   /* ... the largest */
+    uint32_t alive;                   /* alive particles seen */
+    uint32_t nan;                     /* alive particles with a NaN in at least one component */
+    uint32_t reserved[2];             /* written as 0 */
+} HnbBounds;
+typedef struct HnbBoundsDesc {
+    uint32_t struct_size;             /* sizeof(HnbBoundsDesc) */
+    uint32_t attr;                    /* HnbAttr: an f32 attribute of 1..4 components that the layout stores; HNB_ATTR_POSITION gives the AABB */
+    uint32_t flags;                   /* 0 */
+    uint32_t reserved;                /* 0 */
+    void*    dst;                     /* device, 16-byte aligned: HnbBounds records */
+    uint64_t dst_capacity_records;    /* effect form >= 1; program form >= n_instances + 1 */
+} HnbBoundsDesc;
+int hnb_effect_bounds(HnbEffect* fx, const HnbBoundsDesc* desc);
+int hnb_program_bounds(HnbProgram* prog, const HnbBoundsDesc* desc);
+
 /* Readback (synchronising; reporting / parity only, never on the frame path). */
 int hnb_effect_metadata(HnbEffect* fx, HnbEffectMetadata* out);
 int hnb_effect_alive_count(HnbEffect* fx, uint32_t* out);

@@ -24,6 +24,8 @@ def main():
         assets += [ZOO[k]() for k in sorted(ZOO)]
         from helpers import lattice_probe_assets
         assets += lattice_probe_assets(4096)   # (math_probe_asset among them)
+        from test_bounds_abi import trails_vec4
+        assets.append(trails_vec4(4096))
     except Exception as e:  # tests not present: product programs only
         print("warm_jit_cache: zoo skipped:", e)
     # entries are keyed by the generated source and the kernel headers: drop what older builds left behind
