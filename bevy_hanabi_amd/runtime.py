@@ -212,6 +212,25 @@ def export_filter(kind, planes=(), sphere=None, attr=0, lo=0, hi=0, invert=False
     return f
 
 
+class ExportSortFiltered(C.Structure):
+    """HnbExportSortFiltered: the 48-byte form of the sort descriptor - an ExportSort whose struct_size is this struct's, and the host array of
+    filters in front of the sort. Passed where an ExportSort is (export_sort_filtered)."""
+    _fields_ = [("sort", ExportSort), ("filters", C.c_void_p), ("n_filters", C.c_uint32), ("reserved2", C.c_uint32)]
+
+
+def export_sort_filtered(sort, filters):
+    """sort: an ExportSort or a dict of export_sort's keywords; filters: a sequence of ExportFilter or dicts of export_filter's keywords
+    -> (ExportSortFiltered, the ctypes array it points to: keep it alive for as long as the descriptor is used)."""
+    arr = (ExportFilter * max(len(filters), 1))(*[f if isinstance(f, ExportFilter) else export_filter(**f) for f in filters])
+    sf = ExportSortFiltered()
+    s = sort if isinstance(sort, ExportSort) else export_sort(**sort)
+    C.memmove(C.byref(sf.sort), C.byref(s), C.sizeof(ExportSort))
+    sf.sort.struct_size = C.sizeof(ExportSortFiltered)
+    sf.filters = C.cast(arr, C.c_void_p)
+    sf.n_filters = len(filters)
+    return sf, arr
+
+
 class Bounds(C.Structure):
     """HnbBounds (hnb_effect_bounds / hnb_program_bounds): one 48-byte record as the device writes it."""
     _fields_ = [("lo", C.c_float * 4), ("hi", C.c_float * 4), ("alive", C.c_uint32), ("nan", C.c_uint32), ("reserved", C.c_uint32 * 2)]
@@ -553,6 +572,19 @@ class Program:
         fs = filter if isinstance(filter, (list, tuple)) else [filter]
         arr = (ExportFilter * max(len(fs), 1))(*[f if isinstance(f, ExportFilter) else export_filter(**f) for f in fs])
         _check(self._lib.hnb_program_export_filtered(self._h, C.byref(d), arr, len(fs), C.c_void_p(int(offsets_ptr)) if offsets_ptr else None))
+
+    def export_filtered_sorted(self, fields, dst_ptr, stride, capacity_records, count_ptr=None, offsets_ptr=None, *, filter, sort):
+        """hnb_program_export_sorted with an HnbExportSortFiltered, instance scope: of every instance the rows export_filtered() keeps, each
+        segment in the order export_sorted(scope="instance") gives it. `filter`: one filter for all instances or a list with one per instance, as
+        in export_filtered(); `sort`: a dict of export_sort's keywords (key, v, attr, descending) or an ExportSort. offsets_ptr / count_ptr over
+        the kept rows. Asynchronous; the filter array lives until the call has returned."""
+        d = export_desc(fields, dst_ptr, stride, capacity_records, count_ptr)
+        fs = filter if isinstance(filter, (list, tuple)) else [filter]
+        sf, arr = export_sort_filtered(sort, fs)
+        rc = self._lib.hnb_program_export_sorted(self._h, C.byref(d), C.cast(C.byref(sf), C.POINTER(ExportSort)), SORT_SCOPES["instance"],
+                                                 C.c_void_p(int(offsets_ptr)) if offsets_ptr else None)
+        del arr   # (kept alive up to here: the library has read the host array)
+        _check(rc)
 
     def bounds(self, attr, dst_ptr, capacity_records):
         """hnb_program_bounds: a Bounds record per instance at the device address dst_ptr (16-byte aligned), in instance order, and their union behind

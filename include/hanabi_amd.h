@@ -781,6 +781,45 @@ int hnb_effect_export_filtered_sorted(HnbEffect* fx, const HnbExportDesc* desc, 
 int hnb_program_export_filtered(HnbProgram* prog, const HnbExportDesc* desc, const HnbExportFilter* filters, uint32_t n_filters,
                                 uint32_t* out_offsets /* device [n_instances + 1], may be NULL */);
 
+/* Filtered, then sorted export, program form: what a camera sees of a transparent batch, every instance back to front, behind one draw. It is no
+ * call of its own but a second version of the sort descriptor, told apart by the struct_size every descriptor carries: a caller fills an
+ * HnbExportSortFiltered, sets sort.struct_size = sizeof(HnbExportSortFiltered) and passes (const HnbExportSort*)&sf to the sorted calls.
+ *   struct_size 32   HnbExportSort: every alive row, as above.
+ *   struct_size 48   HnbExportSortFiltered: the rows `filters` keep, in the order of `sort`.
+ *   anything else    HNB_ERR_INVALID_ARG.
+ * hnb_program_export_sorted with the 48-byte form and HNB_SORT_SCOPE_INSTANCE
+ *   Instance k's segment is byte for byte what hnb_effect_export_filtered_sorted(effect k, the filter of k, sort) writes: the kept rows in key
+ *   order, ties in list order. Segments follow each other in instance order. out_offsets[k] is the exclusive scan of the KEPT counts, computed on
+ *   the device, out_offsets[n_instances] the kept total. out_count[0] = min(kept total, dst_capacity_records), out_count[1] = the kept total; the
+ *   clamp is global, an instance that is cut keeps the FIRST records of its order, records at and past the written count are not touched.
+ *   `filters` is a HOST array under the rules of the filtered program export above: n_filters == 1, one filter shared by every instance, or
+ *   n_filters == the instance count, one each with the same kind and attr; per-instance rows travel through the program's pinned staging buffer,
+ *   and the staging wait described there is the only host synchronisation of the steady path. The two calls may be interleaved on one program.
+ *   Two identities: with filters that keep every row, dst, out_offsets and out_count are byte for byte those of the 32-byte form; with a key that
+ *   is equal for every row they are hnb_program_export_filtered's.
+ *   Everything else is as in the family: enqueued on the simulation stream, no readback; alive counts, list columns, ring heads and kept counts
+ *   are read on the device; grids are sized from capacity and instance count; no workgroup waits for another; stale AGE is materialised first
+ *   when AGE is a record field, the key or the ATTR_RANGE source; instances that are not simulated export their frozen state; the simulation is
+ *   only read.
+ * hnb_program_export_sorted with the 48-byte form and HNB_SORT_SCOPE_PROGRAM is refused: one order over all instances' kept rows is not built.
+ * hnb_effect_export_sorted with the 48-byte form requires n_filters == 1 and is hnb_effect_export_filtered_sorted(fx, desc, filters, sort).
+ * Errors: HNB_ERR_INVALID_ARG (with hnb_last_error text; nothing is enqueued) for everything the 32-byte form of the call or
+ *   hnb_program_export_filtered rejects (in filters[i] the text names i), for `filters` NULL, n_filters neither 1 nor the instance count (the
+ *   effect form: not 1), reserved2 not 0, and the program scope.
+ * Scratch: owned by the library, per program, one allocation of its own that disturbs neither hnb_program_export_filtered's nor the 32-byte
+ *   form's: the former's layout followed by the latter's instance scope, 20 bytes per slot over all instances plus, above 4096 slots, about 5.6
+ *   more. Allocated by the program's FIRST such export, again - behind one synchronisation of the stream - when the program has gained
+ *   instances since, freed with the program.
+ * The kernels: those of the filtered and of the sorted program export, unchanged, and two that join them (the keys of the rows an instance
+ *   kept; for instances of at most 4096 slots the whole cull and sort of one by one workgroup), which live in a seventh code object that the
+ *   library carries and loads on first use; HNB_ERR_HIP if it cannot be loaded. */
+typedef struct HnbExportSortFiltered {
+    HnbExportSort sort;                /* sort.struct_size = sizeof(HnbExportSortFiltered); everything else as in HnbExportSort */
+    const HnbExportFilter* filters;    /* HOST array of n_filters */
+    uint32_t n_filters;                /* 1: shared by every instance; or the program's instance count */
+    uint32_t reserved2;                /* 0 */
+} HnbExportSortFiltered;
+
 /* ---- Bounds --------------------------------------------------------------------------------------------------------------------
  * Where an effect is as a whole: per component of ONE f32 attribute, the smallest and the largest value among the alive particles - with
  * HNB_ATTR_POSITION the axis-aligned box of the effect. The reference computes no particle bounds (its users set an Aabb by hand or switch frustum
