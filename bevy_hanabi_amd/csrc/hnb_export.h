@@ -1,9 +1,9 @@
-// The packed exports (hnb_effect_export, hnb_program_export, their _sorted forms, hnb_effect_export_filtered, hnb_effect_export_filtered_sorted,
-// hnb_program_export_filtered; include/hanabi_amd.h "Packed output"), shared by the kernels' translation units (hnb_export.hip, hnb_export_sort.hip,
-// hnb_export_filter.hip, hnb_export_cull.hip, hnb_export_filter_prog.hip: a code object each) and the runtime that loads and launches them
-// (hanabi_amd.hip): the kernels' argument blocks, the sort's pass and (instance, slot) arithmetic, the scratch layouts, the kernels by name
-// (ExportKernel) and the launches of a call (export_launch_plan). Plain C++ below the argument blocks: a host compiler takes it, so the tests check
-// the layouts and the plan without a GPU.
+// The packed exports (hnb_effect_export, hnb_program_export, their _sorted forms - with an HnbExportSort or an HnbExportSortFiltered -,
+// hnb_effect_export_filtered, hnb_effect_export_filtered_sorted, hnb_program_export_filtered; include/hanabi_amd.h "Packed output"), shared by the
+// kernels' translation units (hnb_export.hip, hnb_export_sort.hip, hnb_export_filter.hip, hnb_export_cull.hip, hnb_export_filter_prog.hip,
+// hnb_export_cull_prog.hip: a code object each) and the runtime that loads and launches them (hanabi_amd.hip): the kernels' argument blocks, the
+// sort's pass and (instance, slot) arithmetic, the scratch layouts, the kernels by name (ExportKernel) and the launches of a call
+// (export_launch_plan). Plain C++ below the argument blocks: a host compiler takes it, so the tests check the layouts and the plan without a GPU.
 #pragma once
 #include <stdint.h>
 
@@ -264,30 +264,53 @@ HNB_SORT_KEY_FN ExportFilterProgScratch export_filter_prog_scratch_layout(uint32
 }
 
 
+// ---- filtered, then sorted, program form (hnb_program_export_sorted with an HnbExportSortFiltered; kernels: hnb_export_cull_prog.hip, a sixth code
+// object of the exports, and those of units 1, 2 and 5) ----
+// The filtered program export's compaction feeds the sorted program export's instance scope, as the effect form's feeds an effect's sort: the sort
+// and the gather take instance k's row count from kept[k], the rows k_export_offsets scans. Instances of one tile: k_export_cull_tile_inst does
+// everything in front of that scan in one workgroup per instance.
+static_assert(sizeof(HnbExportSortFiltered) == 48, "HnbExportSortFiltered layout");
+
+struct ExportCullProgArgs {
+    ExportFilterProgArgs p;         // as the filtered program export binds it (f.meta: the program's rows), in this form's own scratch
+    ExportSortArgs s;               // as the sorted program export binds its instance scope, except meta: the kept rows (p.f.state)
+};
+
+// The scratch of a program's filtered-then-sorted exports, one allocation: export_filter_prog_scratch_layout, then (at sort_off, a 256-byte
+// boundary) export_sort_scratch_layout of the instance scope. sort.rows == 0: more than 0xFFFFFF00 slots, refused as the sorted export refuses them.
+struct ExportCullProgScratch { ExportFilterProgScratch filter; ExportSortScratch sort; uint64_t sort_off, total; };
+HNB_SORT_KEY_FN ExportCullProgScratch export_cull_prog_scratch_layout(uint32_t n_inst, uint32_t capacity) {
+    ExportCullProgScratch l;
+    l.filter = export_filter_prog_scratch_layout(n_inst, capacity);
+    l.sort = export_sort_scratch_layout(n_inst, capacity, HNB_SORT_SCOPE_INSTANCE);
+    l.sort_off = (l.filter.total + 255u) & ~(uint64_t)255u;
+    l.total = l.sort_off + l.sort.total;
+    return l;
+}
+
+
 // ---- the host path of every form: which kernels there are, and which of them a call launches ----
-// The kernels of the code objects, in the order of their units: the index of a kernel's handle in the context. kExpKernels: those of the first three
-// units; the fourth unit's follow it up to kExpKernelsAll, the fifth unit's follow those, and kExpKernelCount sizes the handle arrays (kExportUnitCount
-// the module array): a later unit is numbered behind the earlier ones, whose values stay.
-enum ExportUnit : uint32_t { kUnitExport, kUnitExportSort, kUnitExportFilter, kUnitExportCull, kExportUnits, kUnitExportFilterProg = kExportUnits, kExportUnitCount };
+// The kernels of the code objects, in the order of their units: the index of a kernel's handle in the context. kExpKernelCount sizes the handle
+// array, kExportUnitCount the module array. A later unit is numbered behind the earlier ones, whose values stay.
+enum ExportUnit : uint32_t { kUnitExport, kUnitExportSort, kUnitExportFilter, kUnitExportCull, kUnitExportFilterProg, kUnitExportCullProg, kExportUnitCount };
 enum ExportKernel : uint32_t {
     kExpRows0, kExpRows1, kExpRows2, kExpRows3, kExpOffsets,                                                    // hnb_export.hip
     kExpSortRows0, kExpSortRows1, kExpSortRows2, kExpSortRows3, kExpSortTile, kExpSortKeys, kExpSortHist, kExpSortScatter,   // hnb_export_sort.hip: one effect,
     kExpSortRowsInst0, kExpSortRowsInst1, kExpSortRowsInst2, kExpSortRowsInst3, kExpSortTileInst, kExpSortKeysInst, kExpSortHistInst, kExpSortScatterInst,   // (tiles, instances),
     kExpSortRowsAll0, kExpSortRowsAll1, kExpSortRowsAll2, kExpSortRowsAll3, kExpSortFill, kExpSortHistAll, kExpSortScatterAll,   // all instances' rows as one space
     kExpFilterRows0, kExpFilterRows1, kExpFilterRows2, kExpFilterRows3, kExpFilterTile, kExpFilterMark, kExpFilterScan, kExpFilterCompact,   // hnb_export_filter.hip
-    kExpKernels,
-    kExpCullTile = kExpKernels, kExpCullKeys,                                                                   // hnb_export_cull.hip
-    kExpKernelsAll,
-    kExpFilterRowsInst0 = kExpKernelsAll, kExpFilterRowsInst1, kExpFilterRowsInst2, kExpFilterRowsInst3,        // hnb_export_filter_prog.hip: (tiles, instances)
+    kExpCullTile, kExpCullKeys,                                                                                 // hnb_export_cull.hip
+    kExpFilterRowsInst0, kExpFilterRowsInst1, kExpFilterRowsInst2, kExpFilterRowsInst3,                         // hnb_export_filter_prog.hip: (tiles, instances)
     kExpFilterTileInst, kExpFilterMarkInst, kExpFilterScanInst, kExpFilterCompactInst,
+    kExpCullTileInst, kExpCullKeysInst,                                                                         // hnb_export_cull_prog.hip: (tiles, instances)
     kExpKernelCount
 };
 
 enum ExportForm : uint32_t { kExportPlain, kExportSorted, kExportFiltered, kExportFilteredSorted };
 // What a launch passes: an argument block by value (the sort's hist and scatter kernels take the pass behind it), or k_export_offsets' five words
-enum ExportArgBlock : uint32_t { kExportArgsRows, kExportArgsSort, kExportArgsSortPass, kExportArgsFilter, kExportArgsOffsets, kExportArgsCull, kExportArgsFilterProg };
+enum ExportArgBlock : uint32_t { kExportArgsRows, kExportArgsSort, kExportArgsSortPass, kExportArgsFilter, kExportArgsOffsets, kExportArgsCull, kExportArgsFilterProg, kExportArgsCullProg };
 struct ExportLaunch { uint32_t kernel, grid_x, grid_y, args, pass; };   // (workgroups of kExportBlock lanes)
-constexpr uint32_t kExportPlanMax = 12, kExportNoMemset = ~0u;
+constexpr uint32_t kExportPlanMax = 13, kExportNoMemset = ~0u;
 struct ExportPlan {
     uint32_t n;                         // launches, in stream order
     uint32_t memset_before;             // a multi-tile sort: bytes [zero_off, zero_off + zero_bytes) of the call's scratch are zeroed in front of launch
@@ -297,15 +320,15 @@ struct ExportPlan {
 
 // The gather of a form, by the LDS image of its records (export_variant)
 HNB_SORT_KEY_FN uint32_t export_rows_kernel(uint32_t form, bool program, uint32_t scope, uint32_t variant) {
-    const uint32_t first = form == kExportFiltered ? (program ? kExpFilterRowsInst0 : kExpFilterRows0) : form == kExportPlain ? kExpRows0 : !program || form == kExportFilteredSorted ? kExpSortRows0 :
-                           scope == HNB_SORT_SCOPE_PROGRAM ? kExpSortRowsAll0 : kExpSortRowsInst0;
+    const uint32_t first = form == kExportFiltered ? (program ? kExpFilterRowsInst0 : kExpFilterRows0) : form == kExportPlain ? kExpRows0 : !program ? kExpSortRows0 :
+                           form == kExportSorted && scope == HNB_SORT_SCOPE_PROGRAM ? kExpSortRowsAll0 : kExpSortRowsInst0;
     return first + variant;
 }
 
 // The launches of one export, in order. `program`: all n_inst instances of a program (plain or sorted in `scope`), else one effect (n_inst and scope
-// are not read). A sorted form's rows must fit (export_sort_scratch_layout(...).rows != 0). kExportFilteredSorted: one effect only. The filtered
-// program form scans KEPT counts, so its k_export_offsets runs behind the instances' compaction counts, not in front. Decides; hanabi_amd.hip
-// run_export_plan executes.
+// are not read). A sorted form's rows must fit (export_sort_scratch_layout(...).rows != 0). kExportFilteredSorted of a program: instance scope. The
+// filtered program forms scan KEPT counts, so their k_export_offsets runs behind the instances' compaction counts, not in front. Decides;
+// hanabi_amd.hip run_export_plan executes.
 HNB_SORT_KEY_FN ExportPlan export_launch_plan(uint32_t form, bool program, uint32_t scope, uint32_t n_inst, uint32_t capacity, uint32_t stride_bytes) {
     ExportPlan pl = {};
     pl.memset_before = kExportNoMemset;
@@ -315,7 +338,7 @@ HNB_SORT_KEY_FN ExportPlan export_launch_plan(uint32_t form, bool program, uint3
     const uint32_t rows = all ? n * capacity : capacity, gy = all ? 1u : n;        // of the gather's row space, and how many of them
     const uint32_t variant = export_variant(stride_bytes), tile_rows = export_tile_rows(variant);
     const auto add = [&pl](uint32_t kernel, uint32_t gx, uint32_t gy, uint32_t args, uint32_t pass = 0u) { pl.launch[pl.n++] = ExportLaunch{kernel, gx, gy, args, pass}; };
-    if (program && form != kExportFiltered) add(kExpOffsets, 1u, 1u, kExportArgsOffsets);
+    if (program && (form == kExportPlain || form == kExportSorted)) add(kExpOffsets, 1u, 1u, kExportArgsOffsets);   // over the alive counts
     if (form == kExportSorted) {
         const ExportSortScratch l = export_sort_scratch_layout(n, capacity, all ? HNB_SORT_SCOPE_PROGRAM : HNB_SORT_SCOPE_INSTANCE);
         const uint32_t tile = program ? kExpSortTileInst : kExpSortTile, keys = all ? kExpSortFill : program ? kExpSortKeysInst : kExpSortKeys;
@@ -344,18 +367,26 @@ HNB_SORT_KEY_FN ExportPlan export_launch_plan(uint32_t form, bool program, uint3
             add(kExpFilterScan, 1u, 1u, kExportArgsFilter);
             add(kExpFilterCompact, tiles, 1u, kExportArgsFilter);
         }
-    } else if (form == kExportFilteredSorted) {
-        const ExportCullScratch l = export_cull_scratch_layout(capacity);
-        if (tiles <= 1u) add(kExpCullTile, 1u, 1u, kExportArgsCull);               // mark, compact into (key, slot) pairs and every pass by one workgroup
-        else {
-            add(kExpFilterMark, tiles, 1u, kExportArgsFilter);
-            add(kExpFilterScan, 1u, 1u, kExportArgsFilter);
-            add(kExpFilterCompact, tiles, 1u, kExportArgsFilter);
-            pl.memset_before = pl.n; pl.zero_off = l.sort_off + l.sort.state_off; pl.zero_bytes = l.sort.zero_bytes;
-            add(kExpCullKeys, tiles, 1u, kExportArgsCull);                         // the kept rows' keys, and pass 0's digit counts
+    } else if (form == kExportFilteredSorted) {                                    // the program form: the effect form's launches per instance, and the scan of the kept counts
+        const uint32_t filter_args = program ? kExportArgsFilterProg : kExportArgsFilter, cull_args = program ? kExportArgsCullProg : kExportArgsCull;
+        const uint32_t mark = program ? kExpFilterMarkInst : kExpFilterMark, scan = program ? kExpFilterScanInst : kExpFilterScan, compact = program ? kExpFilterCompactInst : kExpFilterCompact;
+        const uint32_t tile = program ? kExpCullTileInst : kExpCullTile, keys = program ? kExpCullKeysInst : kExpCullKeys;
+        const uint32_t hist = program ? kExpSortHistInst : kExpSortHist, scatter = program ? kExpSortScatterInst : kExpSortScatter;
+        if (tiles <= 1u) {
+            add(tile, 1u, n, cull_args);                                           // mark, compact into (key, slot) pairs and every pass by one workgroup
+            if (program) add(kExpOffsets, 1u, 1u, kExportArgsOffsets);             // over the kept counts
+        } else {
+            add(mark, tiles, n, filter_args);
+            add(scan, 1u, n, filter_args);
+            if (program) add(kExpOffsets, 1u, 1u, kExportArgsOffsets);             // where the filtered program export has it: only the gather needs it
+            add(compact, tiles, n, filter_args);
+            const ExportSortScratch l = export_sort_scratch_layout(n, capacity, HNB_SORT_SCOPE_INSTANCE);   // (the sort section of either form's scratch)
+            const uint64_t sort_off = program ? export_cull_prog_scratch_layout(n, capacity).sort_off : export_cull_scratch_layout(capacity).sort_off;
+            pl.memset_before = pl.n; pl.zero_off = sort_off + l.state_off; pl.zero_bytes = l.zero_bytes;
+            add(keys, tiles, n, cull_args);                                        // the kept rows' keys, and pass 0's digit counts
             for (uint32_t pass = 0; pass < kExportSortPasses; ++pass) {
-                if (pass) add(kExpSortHist, tiles, 1u, kExportArgsSortPass, pass);
-                add(kExpSortScatter, tiles, 1u, kExportArgsSortPass, pass);
+                if (pass) add(hist, tiles, n, kExportArgsSortPass, pass);
+                add(scatter, tiles, n, kExportArgsSortPass, pass);
             }
         }
     }

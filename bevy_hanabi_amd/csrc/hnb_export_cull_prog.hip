@@ -16,7 +16,7 @@
 // for another.
 #include <hip/hip_runtime.h>
 
-#include "hnb_export_cull_prog.h"
+#include "hnb_export.h"
 #include "hnb_export_filter.hip.h"
 #include "hnb_export_sort.hip.h"
 

@@ -172,7 +172,7 @@ def test_the_exports_five_code_objects_and_tables_are_as_they_were():
     for other in (hb.export_code_path(), hb.export_sort_code_path(), hb.export_filter_code_path(), hb.export_cull_code_path(), hb.export_filter_prog_code_path()):
         assert open(other, "rb").read() in lib
         assert not set(_rows(other)) & set(BOUNDS_KERNELS)
-    assert len(hb.EXPORT_CODE_OBJECTS) == 5
+    assert len(hb.EXPORT_CODE_OBJECTS) == 6
     export_h = open(os.path.join(CSRC, "hnb_export.h")).read()
     assert "bounds" not in export_h.lower()                               # ExportUnit, ExportKernel, ExportArgBlock and export_launch_plan know nothing of the new unit
 

@@ -459,7 +459,7 @@ def test_launch_plan_of_every_form_is_the_designs_table(tmp_path):
         return "?";
     }
     int main() {
-        static_assert(kExpKernels == """ + str(len(kernels)) + r""", "every kernel has a name here");
+        static_assert(kExpCullTile == """ + str(len(kernels)) + r""", "every kernel of the first three units has a name here; the fourth's follow");
         static const char* const args[] = {"rows", "sort", "sort+pass", "filter", "offsets"};
         static_assert(kExportArgsRows == 0 && kExportArgsSort == 1 && kExportArgsSortPass == 2 && kExportArgsFilter == 3 && kExportArgsOffsets == 4, "args[]");
         unsigned form, program, scope, n, cap, stride;

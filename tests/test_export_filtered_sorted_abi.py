@@ -131,9 +131,8 @@ def test_launch_plan_of_the_new_form_is_the_designs_table(tmp_path):
         return "?";
     }
     int main() {
-        static_assert(kExpKernels == 36, "the kernels of the first three units");
-        static_assert(kExpCullTile == kExpKernels && kExpCullKeys == kExpKernels + 1 && kExpKernelsAll == kExpKernels + 2, "the fourth unit's are numbered behind them");
-        static_assert(kUnitExportCull == 3 && kExportUnits == 4, "four units");
+        static_assert(kExpCullTile == 36 && kExpCullKeys == 37 && kExpFilterRowsInst0 == 38, "the fourth unit's are numbered behind the 36 kernels of the first three");
+        static_assert(kUnitExportCull == 3, "the fourth unit");
         static_assert(kExportPlain == 0 && kExportSorted == 1 && kExportFiltered == 2 && kExportFilteredSorted == 3, "forms");
         static const char* const args[] = {"rows", "sort", "sort+pass", "filter", "offsets", "cull"};
         static_assert(kExportArgsRows == 0 && kExportArgsSort == 1 && kExportArgsSortPass == 2 && kExportArgsFilter == 3 && kExportArgsOffsets == 4 && kExportArgsCull == 5, "args[]");

@@ -96,7 +96,7 @@ def test_fifth_code_object_is_built_carried_and_has_its_kernels_without_scratch_
         assert open(other, "rb").read() in lib                           # five embedded code objects
     assert '"-ffp-contract=off"' in inspect.getsource(hb.build_export_filter_prog_code)
     assert "#pragma clang fp contract(off)" in open(os.path.join(CSRC, "hnb_export_filter_prog.hip")).read()
-    assert hb.build_export_filter_prog_code in hb.EXPORT_CODE_OBJECTS and len(hb.EXPORT_CODE_OBJECTS) == 5
+    assert hb.build_export_filter_prog_code in hb.EXPORT_CODE_OBJECTS and len(hb.EXPORT_CODE_OBJECTS) == 6
 
 
 # ---- the launch plan (csrc/hnb_export.h), as a stand-alone host program ---------------------------------------------------------------------------
@@ -126,17 +126,16 @@ def test_launch_plan_of_the_new_form_is_the_designs_table_and_nothing_was_renumb
     }
     int main() {
         // what the two existing plan tests pin
-        static_assert(kExpKernels == 36, "the kernels of the first three units");
-        static_assert(kExpCullTile == kExpKernels && kExpCullKeys == kExpKernels + 1 && kExpKernelsAll == kExpKernels + 2, "the fourth unit's are numbered behind them");
-        static_assert(kUnitExportCull == 3 && kExportUnits == 4, "four units");
+        static_assert(kExpCullTile == 36 && kExpCullKeys == 37 && kExpFilterRowsInst0 == 38, "the fourth unit's are numbered behind the 36 kernels of the first three");
+        static_assert(kUnitExportCull == 3, "the fourth unit");
         static_assert(kExportPlain == 0 && kExportSorted == 1 && kExportFiltered == 2 && kExportFilteredSorted == 3, "forms");
         static_assert(kExportArgsRows == 0 && kExportArgsSort == 1 && kExportArgsSortPass == 2 && kExportArgsFilter == 3 && kExportArgsOffsets == 4 && kExportArgsCull == 5, "args[]");
         static_assert(sizeof(ExportCullArgs) == sizeof(ExportFilterArgs) + sizeof(ExportSortArgs), "one filter block and one sort block");
-        // the fifth unit, behind them
-        static_assert(kUnitExportFilterProg == 4 && kExportUnitCount == 5, "five units");
-        static_assert(kExpFilterRowsInst0 == kExpKernelsAll && kExpFilterRowsInst3 == kExpKernelsAll + 3 && kExpFilterTileInst == kExpKernelsAll + 4 &&
-                      kExpFilterMarkInst == kExpKernelsAll + 5 && kExpFilterScanInst == kExpKernelsAll + 6 && kExpFilterCompactInst == kExpKernelsAll + 7 &&
-                      kExpKernelCount == kExpKernelsAll + 8, "the fifth unit's kernels are numbered behind the fourth's");
+        // the fifth unit, behind them, and the sixth behind it
+        static_assert(kUnitExportFilterProg == 4 && kUnitExportCullProg == 5 && kExportUnitCount == 6, "six units");
+        static_assert(kExpFilterRowsInst0 == 38 && kExpFilterRowsInst1 == 39 && kExpFilterRowsInst2 == 40 && kExpFilterRowsInst3 == 41 && kExpFilterTileInst == 42 &&
+                      kExpFilterMarkInst == 43 && kExpFilterScanInst == 44 && kExpFilterCompactInst == 45, "the fifth unit's kernels are numbered behind the fourth's");
+        static_assert(kExpCullTileInst == 46 && kExpCullKeysInst == 47 && kExpKernelCount == 48, "the sixth unit's kernels are numbered behind the fifth's");
         static_assert(kExportArgsFilterProg == 6, "args[]");
         static_assert(sizeof(ExportFilterProgArgs) == sizeof(ExportFilterArgs) + 16 && sizeof(ExportFilterRow) == 128, "an ExportFilterArgs and the instance words");
         static const char* const args[] = {"rows", "sort", "sort+pass", "filter", "offsets", "cull", "filter+inst"};

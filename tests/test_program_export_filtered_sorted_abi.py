@@ -1,6 +1,6 @@
 """The filtered, then sorted program export (an HnbExportSortFiltered through hnb_program_export_sorted, include/hanabi_amd.h "Packed output")
-without a GPU: the 48-byte descriptor in C99 and in ctypes, no new entry point; its two kernels in a seventh code object with no scratch and no
-spills, next to six older ones whose kernels are what they were; the launch plan and the scratch layout of hnb_export_cull_prog.h from a stand-alone
+without a GPU: the 48-byte descriptor in C99 and in ctypes, no new entry point; its two kernels in a code object of their own with no scratch and
+no spills, next to six older ones whose kernels are what they were; the form's launch plan and scratch layout (hnb_export.h) from a stand-alone
 host program under the address and undefined-behaviour sanitizers, held against the design's table; NULL arguments fail loudly."""
 import ctypes as C
 import inspect
@@ -111,7 +111,7 @@ def test_seventh_code_object_is_gfx950_embedded_and_holds_two_kernels_without_sc
     assert code in lib
     assert '"-ffp-contract=off"' in inspect.getsource(hb.build_export_cull_prog_code)
     assert "#pragma clang fp contract(off)" in open(os.path.join(CSRC, "hnb_export_cull_prog.hip")).read()
-    assert hb.build_export_cull_prog_code not in hb.EXPORT_CODE_OBJECTS and len(hb.EXPORT_CODE_OBJECTS) == 5          # hnb_export.h's tables are closed
+    assert hb.build_export_cull_prog_code in hb.EXPORT_CODE_OBJECTS and len(hb.EXPORT_CODE_OBJECTS) == 6
     assert any(hb.build_export_cull_prog_code in getattr(hb, t) for t in re.findall(r"\b([A-Z_]+_CODE_OBJECTS)\b", inspect.getsource(hb.build_runtime)))
 
 
@@ -123,7 +123,7 @@ def test_the_six_older_code_objects_are_embedded_with_their_kernel_sets_unchange
         assert sorted(_rows(co)) == sorted(kernels), (unit, sorted(_rows(co)))
 
 
-# ---- plan and scratch layout (csrc/hnb_export_cull_prog.h), as a stand-alone host program under the sanitizers -------------------------------------
+# ---- plan and scratch layout (csrc/hnb_export.h), as a stand-alone host program under the sanitizers -----------------------------------------------
 def filter_prog_layout(n, cap):
     """export_filter_prog_scratch_layout restated: (tiles, pitch, [(offset, bytes)] of order, mask, counts, offsets, kept rows, filter rows, total)"""
     up = lambda x: (x + 255) & ~255
@@ -137,39 +137,42 @@ def filter_prog_layout(n, cap):
 
 
 def plan_table(n, cap, stride):
-    """The launches of a call as the issue's table states them: (own unit?, kernel, grid x, grid y, argument block, pass)"""
+    """The launches of a call as the issue's table states them: (kernel, grid x, grid y, argument block, pass)"""
     T = -(-cap // 4096)
     v = {32: 0, 64: 1, 128: 2, 256: 3}[stride]
-    gather = ("old", f"kExpSortRowsInst{v}", -(-cap // (128 if v == 3 else 256)), n, "rows", 0)
+    gather = (f"kExpSortRowsInst{v}", -(-cap // (128 if v == 3 else 256)), n, "rows", 0)
     if T <= 1:
-        return [("own", "kCullProgTileInst", 1, n, "cull+inst", 0), ("old", "kExpOffsets", 1, 1, "offsets", 0), gather]
-    plan = [("old", "kExpFilterMarkInst", T, n, "filter+inst", 0), ("old", "kExpFilterScanInst", 1, n, "filter+inst", 0), ("old", "kExpOffsets", 1, 1, "offsets", 0),
-            ("old", "kExpFilterCompactInst", T, n, "filter+inst", 0), ("own", "kCullProgKeysInst", T, n, "cull+inst", 0), ("old", "kExpSortScatterInst", T, n, "sort+pass", 0)]
+        return [("kExpCullTileInst", 1, n, "cull+inst", 0), ("kExpOffsets", 1, 1, "offsets", 0), gather]
+    plan = [("kExpFilterMarkInst", T, n, "filter+inst", 0), ("kExpFilterScanInst", 1, n, "filter+inst", 0), ("kExpOffsets", 1, 1, "offsets", 0),
+            ("kExpFilterCompactInst", T, n, "filter+inst", 0), ("kExpCullKeysInst", T, n, "cull+inst", 0), ("kExpSortScatterInst", T, n, "sort+pass", 0)]
     for p in (1, 2, 3):
-        plan += [("old", "kExpSortHistInst", T, n, "sort+pass", p), ("old", "kExpSortScatterInst", T, n, "sort+pass", p)]
+        plan += [("kExpSortHistInst", T, n, "sort+pass", p), ("kExpSortScatterInst", T, n, "sort+pass", p)]
     return plan + [gather]
 
 
 def test_plan_and_scratch_layout_under_the_sanitizers_are_the_designs_table(tmp_path):
-    old = ["kExpOffsets", "kExpFilterMarkInst", "kExpFilterScanInst", "kExpFilterCompactInst", "kExpSortHistInst", "kExpSortScatterInst"] + [f"kExpSortRowsInst{v}" for v in range(4)]
+    names = (["kExpOffsets", "kExpFilterMarkInst", "kExpFilterScanInst", "kExpFilterCompactInst", "kExpSortHistInst", "kExpSortScatterInst", "kExpCullTileInst", "kExpCullKeysInst"]
+             + [f"kExpSortRowsInst{v}" for v in range(4)])
     exe = _standalone(tmp_path, "cpl", r"""
     #include <cstdio>
     #include <cstdint>
-    #include "hnb_export_cull_prog.h"
+    #include "hnb_export.h"
     using namespace hnb;
-    static const char* old_name(uint32_t k) {
+    static const char* kernel_name(uint32_t k) {
         switch (k) {
-    """ + "\n".join(f'        case {k}: return "{k}";' for k in old) + r"""
+    """ + "\n".join(f'        case {k}: return "{k}";' for k in names) + r"""
         }
         return "?";
     }
     int main() {
-        // the tables of hnb_export.h are what the older plan tests pin; this unit is numbered apart from them
-        static_assert(kExportUnitCount == 5 && kExpKernelCount == kExpKernelsAll + 8 && kExportPlanMax == 12 && kExportArgsFilterProg == 6, "hnb_export.h is closed");
-        static_assert(kCullProgTileInst == 0 && kCullProgKeysInst == 1 && kCullProgKernelCount == 2 && kCullProgArgs == 7 && kCullProgPlanMax == 13, "this unit's numbering");
+        static_assert(kExportPlanMax == 13 && kExportArgsCullProg == 7, "the longest plan and the last argument block are this form's");
         static_assert(sizeof(ExportCullProgArgs) == sizeof(ExportFilterProgArgs) + sizeof(ExportSortArgs) && sizeof(HnbExportSortFiltered) == 48, "one block of each");
         static const char* const args[] = {"rows", "sort", "sort+pass", "filter", "offsets", "cull", "filter+inst", "cull+inst"};
-        static const char* const own[] = {"kCullProgTileInst", "kCullProgKeysInst"};
+        for (uint32_t variant = 0; variant < kExportVariants; ++variant)         // the gather of the filtered and sorted forms: an effect's, a program's per instance
+            for (uint32_t scope = HNB_SORT_SCOPE_INSTANCE; scope <= HNB_SORT_SCOPE_PROGRAM; ++scope) {
+                if (export_rows_kernel(kExportFilteredSorted, false, scope, variant) != kExpSortRows0 + variant) return 4;
+                if (export_rows_kernel(kExportFilteredSorted, true, HNB_SORT_SCOPE_INSTANCE, variant) != kExpSortRowsInst0 + variant) return 5;
+            }
         unsigned long long n, cap, stride;
         while (std::scanf("%llu %llu %llu", &n, &cap, &stride) == 3) {
             const ExportCullProgScratch l = export_cull_prog_scratch_layout((uint32_t)n, (uint32_t)cap);
@@ -181,13 +184,13 @@ def test_plan_and_scratch_layout_under_the_sanitizers_are_the_designs_table(tmp_
             for (unsigned long long x : v) std::printf(" %llu", x);
             std::printf("\n");
             if (l.sort.rows == 0) { std::printf("P refused\n"); continue; }      // more than 0xFFFFFF00 slots: no plan is asked for
-            const CullProgPlan pl = cull_prog_launch_plan((uint32_t)n, (uint32_t)cap, (uint32_t)stride);
-            if (pl.n > kCullProgPlanMax) return 2;
+            const ExportPlan pl = export_launch_plan(kExportFilteredSorted, true, HNB_SORT_SCOPE_INSTANCE, (uint32_t)n, (uint32_t)cap, (uint32_t)stride);
+            if (pl.n > kExportPlanMax) return 2;
             std::printf("P %u %d %llu %llu", pl.n, pl.memset_before == kExportNoMemset ? -1 : (int)pl.memset_before, (unsigned long long)pl.zero_off, (unsigned long long)pl.zero_bytes);
             for (uint32_t i = 0; i < pl.n; ++i) {
-                const CullProgLaunch& ln = pl.launch[i];
-                if (ln.own && ln.kernel >= kCullProgKernelCount) return 3;
-                std::printf(" %s %s %u %u %s %u", ln.own ? "own" : "old", ln.own ? own[ln.kernel] : old_name(ln.kernel), ln.grid_x, ln.grid_y, args[ln.args], ln.pass);
+                const ExportLaunch& ln = pl.launch[i];
+                if (ln.kernel >= kExpKernelCount || ln.args > kExportArgsCullProg) return 3;
+                std::printf(" %s %u %u %s %u", kernel_name(ln.kernel), ln.grid_x, ln.grid_y, args[ln.args], ln.pass);
             }
             std::printf("\n");
         }
@@ -211,12 +214,12 @@ def test_plan_and_scratch_layout_under_the_sanitizers_are_the_designs_table(tmp_
             continue
         p = plan.split()
         count, memset, zero_off, zero_bytes = int(p[1]), int(p[2]), int(p[3]), int(p[4])
-        got = [(p[i], p[i + 1], int(p[i + 2]), int(p[i + 3]), p[i + 4], int(p[i + 5])) for i in range(5, len(p), 6)]
+        got = [(p[i], int(p[i + 1]), int(p[i + 2]), p[i + 3], int(p[i + 4])) for i in range(5, len(p), 5)]
         assert count == len(got) and got == plan_table(n, cap, stride), (what, got)
         if cap <= 4096:
             assert count == 3 and memset == -1, what
         else:                                                            # thirteen launches, and one memset of the sort's state words and group sums in front of the keys kernel
-            assert count == 13 and memset == 4 and got[memset][1] == "kCullProgKeysInst", what
+            assert count == 13 and memset == 4 and got[memset][0] == "kExpCullKeysInst", what
             state_off, hist_off = w[23], w[25]
             assert zero_off == sort_off + state_off and zero_bytes == hist_off - state_off and zero_off + zero_bytes <= total, what
-        assert all(gx >= 1 and 1 <= gy <= 65_535 for _, _, gx, gy, _, _ in got), what
+        assert all(gx >= 1 and 1 <= gy <= 65_535 for _, gx, gy, _, _ in got), what

@@ -1,5 +1,6 @@
-"""Host cost of one packed-export call, per form: hnb_effect_export, hnb_program_export, hnb_effect_export_sorted, hnb_program_export_sorted and
-hnb_effect_export_filtered, each enqueued CALLS times between two synchronisations, WINDOWS times over.
+"""Host cost of one packed-export call, per form: hnb_effect_export, hnb_program_export, hnb_effect_export_sorted, hnb_program_export_sorted (both
+scopes, and with an HnbExportSortFiltered), hnb_effect_export_filtered, hnb_program_export_filtered, hnb_effect_export_filtered_sorted - and of
+hnb_program_bounds, which shares their loader -, each enqueued CALLS times between two synchronisations, WINDOWS times over.
 
 One effect and a program of three instances, 4096 slots each, records of 32 bytes: every form is on its one-launch-per-stage path, where the time of a
 call is the library's host path and the launches behind it, not the kernels. The descriptions are built once; the loop calls the C ABI directly.
@@ -48,13 +49,21 @@ def main():
     d = runtime.export_desc(fields, dst.data_ptr(), stride, 3 * cap, cnt.data_ptr())
     s = runtime.export_sort("depth", (0.3, -0.5, 0.8), 0, False)
     f = runtime.export_filter("planes", [(1.0, 0.0, -0.5, 0.0)], None, 0, 0, 0, False)
-    pd, ps, pf = C.byref(d), C.byref(s), C.byref(f)
+    sf, sf_filters = runtime.export_sort_filtered(s, [f])               # the 48-byte form: the same key, the same one filter for every instance
+    bounds = torch.zeros((4 * 12,), dtype=torch.int32, device="cuda")   # a record per instance and their union
+    b = runtime.bounds_desc(pos, bounds.data_ptr(), 4)
+    pd, ps, pf, pb = C.byref(d), C.byref(s), C.byref(f), C.byref(b)
+    psf = C.cast(C.byref(sf), C.POINTER(runtime.ExportSort))
     forms = [("effect_export", lambda: lib.hnb_effect_export(fx._h, pd)),
              ("program_export", lambda: lib.hnb_program_export(prog._h, pd, None)),
              ("effect_export_sorted", lambda: lib.hnb_effect_export_sorted(fx._h, pd, ps)),
              ("program_export_sorted/instance", lambda: lib.hnb_program_export_sorted(prog._h, pd, ps, runtime.SORT_SCOPE_INSTANCE, None)),
              ("program_export_sorted/program", lambda: lib.hnb_program_export_sorted(prog._h, pd, ps, runtime.SORT_SCOPE_PROGRAM, None)),
-             ("effect_export_filtered", lambda: lib.hnb_effect_export_filtered(fx._h, pd, pf))]
+             ("effect_export_filtered", lambda: lib.hnb_effect_export_filtered(fx._h, pd, pf)),
+             ("program_export_filtered", lambda: lib.hnb_program_export_filtered(prog._h, pd, pf, 1, None)),
+             ("effect_export_filtered_sorted", lambda: lib.hnb_effect_export_filtered_sorted(fx._h, pd, pf, ps)),
+             ("program_export_filtered_sorted", lambda: lib.hnb_program_export_sorted(prog._h, pd, psf, runtime.SORT_SCOPE_INSTANCE, None)),
+             ("program_bounds", lambda: lib.hnb_program_bounds(prog._h, pb))]
     print(f"{args.label}: {args.calls} calls per window, {args.windows} windows, {args.alive} of {cap} slots alive, us per call")
     for name, call in forms:
         for _ in range(50):                                              # loads the code object, allocates the scratch
