@@ -34,6 +34,8 @@ ABI_SYMBOLS = [
     "hnb_effect_export_filtered", "hnb_effect_export_filtered_sorted", "hnb_program_export_filtered",
     "hnb_effect_bounds", "hnb_program_bounds",
 ]
+# ... and the entry point include/hanabi_amd_binned.h declares
+ABI_BINNED_SYMBOLS = ["hnb_effect_export_binned"]
 
 # hnb_ctx_set_option (include/hanabi_amd.h): name -> option id
 OPTIONS = {"list_order": 1, "alternate": 2, "skip_lists": 3, "age_cohort": 4, "cull_lifetime": 5, "horizon": 6, "transpose": 7, "scene_merge": 8,
@@ -231,6 +233,27 @@ def export_sort_filtered(sort, filters):
     return sf, arr
 
 
+BIN_MAX_CELLS = 1 << 24   # HNB_BIN_MAX_CELLS
+
+
+class ExportBins(C.Structure):
+    """HnbExportBins (hnb_effect_export_binned): the uniform grid the records are ordered by, and the device table of the cells' first records."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("dims", C.c_uint32 * 3), ("reserved", C.c_uint32), ("origin", C.c_float * 3),
+                ("inv_cell", C.c_float * 3), ("cell_start", C.c_void_p)]
+
+
+def export_bins(dims, origin, inv_cell, cell_start_ptr):
+    """dims: cells along x, y, z; origin: the grid's lowest corner; inv_cell: 1 / cell edge per axis (floats, taken as binary32); cell_start_ptr:
+    the device address of dims[0] * dims[1] * dims[2] + 2 words -> ExportBins."""
+    g = ExportBins()
+    g.struct_size = C.sizeof(ExportBins)
+    g.dims = (C.c_uint32 * 3)(*[int(x) for x in dims])
+    g.origin = (C.c_float * 3)(*[float(x) for x in origin])
+    g.inv_cell = (C.c_float * 3)(*[float(x) for x in inv_cell])
+    g.cell_start = C.c_void_p(int(cell_start_ptr)) if cell_start_ptr else None
+    return g
+
+
 class Bounds(C.Structure):
     """HnbBounds (hnb_effect_bounds / hnb_program_bounds): one 48-byte record as the device writes it."""
     _fields_ = [("lo", C.c_float * 4), ("hi", C.c_float * 4), ("alive", C.c_uint32), ("nan", C.c_uint32), ("reserved", C.c_uint32 * 2)]
@@ -323,6 +346,7 @@ def load_library():
         lib.hnb_program_export_filtered.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.POINTER(ExportFilter), C.c_uint32, C.c_void_p]
         lib.hnb_effect_bounds.argtypes = [C.c_void_p, C.POINTER(BoundsDesc)]
         lib.hnb_program_bounds.argtypes = [C.c_void_p, C.POINTER(BoundsDesc)]
+        lib.hnb_effect_export_binned.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.POINTER(ExportBins)]
         _lib = lib
     return _lib
 
@@ -719,6 +743,16 @@ class Effect:
         f = export_filter(**filter)
         s = export_sort(**sort)
         _check(self._lib.hnb_effect_export_filtered_sorted(self._h, C.byref(d), C.byref(f), C.byref(s)))
+
+    def export_binned(self, fields, dst_ptr, stride, capacity_records, count_ptr=None, *, dims, origin, inv_cell, cell_start_ptr):
+        """hnb_effect_export_binned: the records of export(), ordered by the cell of a uniform grid of dims[0] x dims[1] x dims[2] cells that holds
+        their POSITION - lowest corner `origin`, 1 / cell edge `inv_cell` per axis; particles outside the grid come last, particles of one cell
+        keep list order. cell_start_ptr (device u32[n_cells + 2], 16-byte aligned): entry c = the records in cells below c, so cell c's records
+        are [entry c, entry c + 1), entry n_cells the first outside record and entry n_cells + 1 the alive count. A destination of K records
+        receives the first K of the order; the table is not clamped."""
+        d = export_desc(fields, dst_ptr, stride, capacity_records, count_ptr)
+        g = export_bins(dims, origin, inv_cell, cell_start_ptr)
+        _check(self._lib.hnb_effect_export_binned(self._h, C.byref(d), C.byref(g)))
 
     def bounds(self, attr, dst_ptr, capacity_records=1):
         """hnb_effect_bounds: one Bounds record at the device address dst_ptr (16-byte aligned) - per component of the f32 attribute `attr` the
