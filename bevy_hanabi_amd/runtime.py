@@ -36,6 +36,8 @@ ABI_SYMBOLS = [
 ]
 # ... and the entry point include/hanabi_amd_binned.h declares
 ABI_BINNED_SYMBOLS = ["hnb_effect_export_binned"]
+# ... and the one include/hanabi_amd_import.h declares
+ABI_IMPORT_SYMBOLS = ["hnb_effect_import"]
 
 # hnb_ctx_set_option (include/hanabi_amd.h): name -> option id
 OPTIONS = {"list_order": 1, "alternate": 2, "skip_lists": 3, "age_cohort": 4, "cull_lifetime": 5, "horizon": 6, "transpose": 7, "scene_merge": 8,
@@ -153,6 +155,36 @@ def export_desc(fields, dst_ptr, stride, capacity_records, count_ptr=None):
     d.dst = C.c_void_p(int(dst_ptr))
     d.dst_capacity_records = int(capacity_records)
     d.out_count = C.c_void_p(int(count_ptr)) if count_ptr else None
+    return d
+
+
+IMPORT_ROWS, IMPORT_IDS = 0, 1   # HNB_IMPORT_*
+IMPORT_MODES = {"rows": IMPORT_ROWS, "ids": IMPORT_IDS}
+
+
+class ImportDesc(C.Structure):
+    """HnbImportDesc (hnb_effect_import): the record layout and the device buffers of a packed input. `fields` are the exports' ExportField: a
+    field's dst_offset is its byte offset in the source record."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_fields", C.c_uint32), ("record_stride", C.c_uint32), ("mode", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32), ("src", C.c_void_p), ("src_capacity_records", C.c_uint64), ("src_count", C.c_void_p), ("out_count", C.c_void_p),
+                ("fields", ExportField * EXPORT_MAX_FIELDS)]
+
+
+def import_desc(fields, src_ptr, stride, capacity_records, mode=IMPORT_ROWS, src_count_ptr=None, out_count_ptr=None):
+    """fields: (attribute id, byte offset) pairs, or ExportField objects; mode: IMPORT_ROWS / IMPORT_IDS or "rows" / "ids" -> ImportDesc. More than
+    EXPORT_MAX_FIELDS fields keep their count: the library refuses them."""
+    d = ImportDesc()
+    d.struct_size = C.sizeof(ImportDesc)
+    fields = list(fields)
+    d.n_fields = len(fields)
+    for i, f in enumerate(fields[:EXPORT_MAX_FIELDS]):
+        d.fields[i] = f if isinstance(f, ExportField) else ExportField(int(f[0]), 0, int(f[1]))
+    d.record_stride = int(stride)
+    d.mode = IMPORT_MODES[mode] if isinstance(mode, str) else int(mode)
+    d.src = C.c_void_p(int(src_ptr)) if src_ptr else None
+    d.src_capacity_records = int(capacity_records)
+    d.src_count = C.c_void_p(int(src_count_ptr)) if src_count_ptr else None
+    d.out_count = C.c_void_p(int(out_count_ptr)) if out_count_ptr else None
     return d
 
 
@@ -347,6 +379,7 @@ def load_library():
         lib.hnb_effect_bounds.argtypes = [C.c_void_p, C.POINTER(BoundsDesc)]
         lib.hnb_program_bounds.argtypes = [C.c_void_p, C.POINTER(BoundsDesc)]
         lib.hnb_effect_export_binned.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.POINTER(ExportBins)]
+        lib.hnb_effect_import.argtypes = [C.c_void_p, C.POINTER(ImportDesc)]
         _lib = lib
     return _lib
 
@@ -753,6 +786,16 @@ class Effect:
         d = export_desc(fields, dst_ptr, stride, capacity_records, count_ptr)
         g = export_bins(dims, origin, inv_cell, cell_start_ptr)
         _check(self._lib.hnb_effect_export_binned(self._h, C.byref(d), C.byref(g)))
+
+    def import_records(self, fields, src_ptr, stride, capacity_records, mode=IMPORT_ROWS, src_count_ptr=None, out_count_ptr=None):
+        """hnb_effect_import, the inverse of export(): the records at the device address src_ptr are written into the planes of the particles they
+        belong to - mode IMPORT_ROWS: record r belongs to row r of the alive list; IMPORT_IDS: to the particle its ID field (slot_base + slot)
+        names, in any order and as any subset; records naming a dead slot or none of this effect are skipped. At most capacity_records records
+        and, with src_count_ptr (device u32), at most that many are read; out_count_ptr (device u32[2], optional) receives the records applied
+        and skipped. Raw device addresses; enqueued on the simulation stream behind everything so far, nothing synchronises; later frames see the
+        planes as after write_attr of the same values."""
+        d = import_desc(fields, src_ptr, stride, capacity_records, mode, src_count_ptr, out_count_ptr)
+        _check(self._lib.hnb_effect_import(self._h, C.byref(d)))
 
     def bounds(self, attr, dst_ptr, capacity_records=1):
         """hnb_effect_bounds: one Bounds record at the device address dst_ptr (16-byte aligned) - per component of the f32 attribute `attr` the
