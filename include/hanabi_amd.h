@@ -897,13 +897,15 @@ int hnb_effect_write_attr(HnbEffect* fx, uint32_t attr, const void* src, size_t 
  *   byte of a slot says which of the two lists it is in, every alive particle of a program that reaps by lifetime has age < lifetime
  *   (src/lib.rs:1223-1258), and the device raised no fault (HnbEffectMetadata::fault: a host-side proof that did not hold).
  * hnb_effect_compare: two effects of the same layout on the same device, bit for bit: the eight counter words, the alive rows, the dead rows,
- *   every attribute plane over every slot. What bench.py holds the state its timed frames produced against: a second context that replayed the
+ *   every attribute plane over every slot. It does not compare the alive bytes: hnb_effect_check on each side holds them against that side's
+ *   lists. The lists are compared row by row only where both sides carry the same alive_count; an alive_count above the capacity (no state of
+ *   an effect) counts as a difference in that counter word even where both sides carry the same one, and neither list is read. What bench.py holds the state its timed frames produced against: a second context that replayed the
  *   same frames with every proof and hint of hnb_ctx_set_option switched off. */
 typedef struct HnbEffectCheck {
     uint32_t ok;                     /* 1: every count below is zero */
     uint32_t capacity, alive_count;
     uint32_t bad_slots;              /* list rows that name a slot >= capacity */
-    uint32_t duplicate_slots;        /* slots named by more than one row */
+    uint32_t duplicate_slots;        /* rows that name a slot another row already named: in-range rows minus distinct slots (a slot named three times counts 2) */
     uint32_t alive_byte_mismatches;  /* slots whose alive byte disagrees with the list that names them */
     uint32_t alive_past_lifetime;    /* alive particles with !(age < lifetime) (0 for programs that do not reap by lifetime) */
     uint32_t fault;                  /* HnbEffectMetadata::fault */
