@@ -26,13 +26,12 @@
 // Nothing is read back: every decision above is taken on the device from the same few words.
 #pragma once
 #include "hnb_kernels.hip.h"
+#include "hnb_program.h"
 
 namespace hnb {
 
-// Items per workgroup in the sort kernels (measured: 16384-item tiles leave the chip under-filled at 4M keys
-// and are 30 % slower overall), and tiles per group of the two-level digit offsets.
-constexpr uint32_t kSortTile = 4096;
-constexpr uint32_t kSortGroup = 32;
+// (kSortTile - items per workgroup in the sort kernels - and kSortGroup - tiles per group of the two-level digit offsets - are hnb_program.h's:
+// the slab layout sizes the scratch by them)
 
 struct SortArgs {
     uint32_t capacity, chunks_per_inst;   // chunks_per_inst = ceil(capacity / kSortTile) here

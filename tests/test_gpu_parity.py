@@ -149,7 +149,7 @@ def test_zoo_through_the_slot_major_init(name, kernels):
         frames.append(Frame(1 / 60 if f % 7 else 1 / 30, (cap // 9) if f % 11 == 0 else (cap if f == 40 else 0), frame_seed(f), xf, time=f / 60.0))
     g = GpuRunner(asset, ctx=c)
     run_script(g, frames, OracleRunner(asset), every=10)
-    # eligible (hanabi_amd.hip slot_init_eligible): no ribbons, no parent, the init stream reads neither PARTICLE_COUNTER nor a parent particle
+    # eligible (hnb_program.h slot_init_eligible): no ribbons, no parent, the init stream reads neither PARTICLE_COUNTER nor a parent particle
     hdr = struct.unpack_from("<24I", g.blob)
     flags, init_len, init_off = hdr[4], hdr[9], hdr[17]
     ops = [struct.unpack_from("<I", g.blob, init_off + 8 * i)[0] & 0xFF for i in range(init_len)]

@@ -23,7 +23,7 @@ HEADER_WORDS = 24   # HnbProgramHeader: 24 u32 (include/hanabi_amd.h)
 def _driver(tmp_path_factory):
     out = os.path.join(ROOT, "tests", "validator_fuzz", "run_blobs")
     src = os.path.join(ROOT, "tests", "validator_fuzz", "run_blobs.cpp")
-    deps = [src, os.path.join(ROOT, "tests", "cpu_vm", "cpu_vm.cpp")] + [os.path.join(ROOT, "bevy_hanabi_amd", "csrc", f) for f in ("hnb_vm.h", "hnb_math.h")]
+    deps = [src, os.path.join(ROOT, "tests", "cpu_vm", "cpu_vm.cpp")] + [os.path.join(ROOT, "bevy_hanabi_amd", "csrc", f) for f in ("hnb_vm.h", "hnb_math.h", "hnb_program.h", "hnb_dev.h", "hnb_plan.h")]
     if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
         subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address", "-fno-omit-frame-pointer", "-ffp-contract=off",
                                "-Wno-unknown-pragmas", "-DHNB_VM_BOUNDS_CHECK", src, "-o", out])

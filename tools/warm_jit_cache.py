@@ -28,6 +28,11 @@ def main():
         assets.append(trails_vec4(4096))
     except Exception as e:  # tests not present: product programs only
         print("warm_jit_cache: zoo skipped:", e)
+    try:
+        from golden.make_program_goldens import kernel_info_cases
+        assets += [a for a, _ in kernel_info_cases().values()]   # (tests/test_gpu_program_facts.py)
+    except Exception as e:
+        print("warm_jit_cache: kernel-info programs skipped:", e)
     # entries are keyed by the generated source and the kernel headers: drop what older builds left behind
     cache = os.path.join(ROOT, "bevy_hanabi_amd", "jit_cache")
     if os.path.isdir(cache) and not os.environ.get("HNB_JIT_CACHE"):
