@@ -38,6 +38,8 @@ ABI_SYMBOLS = [
 ABI_BINNED_SYMBOLS = ["hnb_effect_export_binned"]
 # ... and the one include/hanabi_amd_import.h declares
 ABI_IMPORT_SYMBOLS = ["hnb_effect_import"]
+# ... and the two include/hanabi_amd_deposit.h declares
+ABI_DEPOSIT_SYMBOLS = ["hnb_effect_deposit", "hnb_program_deposit"]
 
 # hnb_ctx_set_option (include/hanabi_amd.h): name -> option id
 OPTIONS = {"list_order": 1, "alternate": 2, "skip_lists": 3, "age_cohort": 4, "cull_lifetime": 5, "horizon": 6, "transpose": 7, "scene_merge": 8,
@@ -306,6 +308,41 @@ def bounds_desc(attr, dst_ptr, capacity_records):
     return d
 
 
+DEPOSIT_MAX_CHANNELS = 4     # HNB_DEPOSIT_MAX_CHANNELS
+DEPOSIT_ACCUMULATE = 0x1     # HNB_DEPOSIT_ACCUMULATE
+
+
+class DepositChannel(C.Structure):
+    """HnbDepositChannel: component `comp` of the f32 attribute `attr`, summed in units of 2^-frac_bits."""
+    _fields_ = [("attr", C.c_uint32), ("comp", C.c_uint32), ("frac_bits", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class DepositDesc(C.Structure):
+    """HnbDepositDesc (hnb_effect_deposit / hnb_program_deposit): the uniform grid, the channels and the device buffers of a deposit."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("dims", C.c_uint32 * 3), ("n_channels", C.c_uint32), ("origin", C.c_float * 3),
+                ("inv_cell", C.c_float * 3), ("channels", DepositChannel * DEPOSIT_MAX_CHANNELS), ("count", C.c_void_p), ("sums", C.c_void_p), ("out_stats", C.c_void_p)]
+
+
+def deposit_desc(dims, origin, inv_cell, count_ptr, channels=(), sums_ptr=None, stats_ptr=None, accumulate=False):
+    """dims, origin, inv_cell: export_bins' grid; channels: (attribute id, component, frac_bits) triples or DepositChannel objects; count_ptr:
+    the device address of n_cells + 1 u32; sums_ptr: of (n_cells + 1) * len(channels) i64 (None without channels); stats_ptr: of 4 u32 or None
+    -> DepositDesc. More than DEPOSIT_MAX_CHANNELS channels keep their count: the library refuses them."""
+    d = DepositDesc()
+    d.struct_size = C.sizeof(DepositDesc)
+    d.flags = DEPOSIT_ACCUMULATE if accumulate else 0
+    d.dims = (C.c_uint32 * 3)(*[int(x) for x in dims])
+    d.origin = (C.c_float * 3)(*[float(x) for x in origin])
+    d.inv_cell = (C.c_float * 3)(*[float(x) for x in inv_cell])
+    channels = list(channels)
+    d.n_channels = len(channels)
+    for i, ch in enumerate(channels[:DEPOSIT_MAX_CHANNELS]):
+        d.channels[i] = ch if isinstance(ch, DepositChannel) else DepositChannel(int(ch[0]), int(ch[1]), int(ch[2]), 0)
+    d.count = C.c_void_p(int(count_ptr)) if count_ptr else None
+    d.sums = C.c_void_p(int(sums_ptr)) if sums_ptr else None
+    d.out_stats = C.c_void_p(int(stats_ptr)) if stats_ptr else None
+    return d
+
+
 _lib = None
 
 
@@ -380,6 +417,8 @@ def load_library():
         lib.hnb_program_bounds.argtypes = [C.c_void_p, C.POINTER(BoundsDesc)]
         lib.hnb_effect_export_binned.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.POINTER(ExportBins)]
         lib.hnb_effect_import.argtypes = [C.c_void_p, C.POINTER(ImportDesc)]
+        lib.hnb_effect_deposit.argtypes = [C.c_void_p, C.POINTER(DepositDesc)]
+        lib.hnb_program_deposit.argtypes = [C.c_void_p, C.POINTER(DepositDesc)]
         _lib = lib
     return _lib
 
@@ -650,6 +689,11 @@ class Program:
         d = bounds_desc(attr, dst_ptr, capacity_records)
         _check(self._lib.hnb_program_bounds(self._h, C.byref(d)))
 
+    def deposit(self, dims, origin, inv_cell, count_ptr, channels=(), sums_ptr=None, stats_ptr=None, accumulate=False):
+        """hnb_program_deposit: Effect.deposit over every instance of the program, all into the one grid; the stats are the totals."""
+        d = deposit_desc(dims, origin, inv_cell, count_ptr, channels, sums_ptr, stats_ptr, accumulate)
+        _check(self._lib.hnb_program_deposit(self._h, C.byref(d)))
+
     def kernel_info(self):
         """Which kernels run this program: 'init=jit|interp|none update=aot-stream:<name>|jit-stream|jit-generic|interp-*'."""
         buf = C.create_string_buffer(4096)
@@ -803,6 +847,15 @@ class Effect:
         with a NaN. Asynchronous: enqueued on the simulation stream, nothing is read back."""
         d = bounds_desc(attr, dst_ptr, capacity_records)
         _check(self._lib.hnb_effect_bounds(self._h, C.byref(d)))
+
+    def deposit(self, dims, origin, inv_cell, count_ptr, channels=(), sums_ptr=None, stats_ptr=None, accumulate=False):
+        """hnb_effect_deposit: the alive particles summed into the uniform grid of export_binned - count_ptr (device u32[n_cells + 1], 16-byte
+        aligned): the particles per cell, entry n_cells the outside bin; sums_ptr (device i64[(n_cells + 1) * len(channels)], channel-minor):
+        per channel (attribute id, component, frac_bits) the sum of round(v * 2^frac_bits) over the cell's particles, exact to the bit;
+        stats_ptr (device u32[4], optional): deposited, outside, rejected contributions, 0. accumulate: add onto what is there instead of clearing
+        first. Raw device addresses; enqueued on the simulation stream, nothing is read back. As f32: sums.to(torch.float32) * 2.0**-frac_bits."""
+        d = deposit_desc(dims, origin, inv_cell, count_ptr, channels, sums_ptr, stats_ptr, accumulate)
+        _check(self._lib.hnb_effect_deposit(self._h, C.byref(d)))
 
     def check(self):
         """hnb_effect_check: list permutation, alive bytes, age < lifetime, fault flag - on the device; a dict with "ok"."""
