@@ -40,6 +40,8 @@ ABI_BINNED_SYMBOLS = ["hnb_effect_export_binned"]
 ABI_IMPORT_SYMBOLS = ["hnb_effect_import"]
 # ... and the two include/hanabi_amd_deposit.h declares
 ABI_DEPOSIT_SYMBOLS = ["hnb_effect_deposit", "hnb_program_deposit"]
+# ... and the one include/hanabi_amd_sample.h declares
+ABI_SAMPLE_SYMBOLS = ["hnb_effect_sample"]
 
 # hnb_ctx_set_option (include/hanabi_amd.h): name -> option id
 OPTIONS = {"list_order": 1, "alternate": 2, "skip_lists": 3, "age_cohort": 4, "cull_lifetime": 5, "horizon": 6, "transpose": 7, "scene_merge": 8,
@@ -343,6 +345,44 @@ def deposit_desc(dims, origin, inv_cell, count_ptr, channels=(), sums_ptr=None, 
     return d
 
 
+SAMPLE_MAX_CHANNELS = 4               # HNB_SAMPLE_MAX_CHANNELS
+SAMPLE_NEAREST, SAMPLE_TRILINEAR = 0, 1   # HNB_SAMPLE_NEAREST, HNB_SAMPLE_TRILINEAR
+SAMPLE_SET, SAMPLE_ADD = 0, 1         # HNB_SAMPLE_SET, HNB_SAMPLE_ADD
+
+
+class SampleChannel(C.Structure):
+    """HnbSampleChannel: a channel of the field goes into component `comp` of the f32 attribute `attr`, stored (SAMPLE_SET) or added (SAMPLE_ADD)."""
+    _fields_ = [("attr", C.c_uint32), ("comp", C.c_uint32), ("op", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SampleDesc(C.Structure):
+    """HnbSampleDesc (hnb_effect_sample): the uniform grid, the mode, the scale, the destinations and the device field of a sample."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("dims", C.c_uint32 * 3), ("n_channels", C.c_uint32), ("origin", C.c_float * 3),
+                ("inv_cell", C.c_float * 3), ("mode", C.c_uint32), ("scale", C.c_float), ("channels", SampleChannel * SAMPLE_MAX_CHANNELS), ("field", C.c_void_p),
+                ("out_stats", C.c_void_p)]
+
+
+def sample_desc(dims, origin, inv_cell, field_ptr, channels, mode=SAMPLE_TRILINEAR, scale=1.0, stats_ptr=None):
+    """dims, origin, inv_cell: export_bins' grid; field_ptr: the device address of n_cells * len(channels) f32, channel-minor; channels: per channel
+    of the field an (attribute id, component, op) triple or a SampleChannel; stats_ptr: the device address of 4 u32 or None -> SampleDesc. More than
+    SAMPLE_MAX_CHANNELS channels keep their count: the library refuses them."""
+    d = SampleDesc()
+    d.struct_size = C.sizeof(SampleDesc)
+    d.flags = 0
+    d.dims = (C.c_uint32 * 3)(*[int(x) for x in dims])
+    d.origin = (C.c_float * 3)(*[float(x) for x in origin])
+    d.inv_cell = (C.c_float * 3)(*[float(x) for x in inv_cell])
+    d.mode = int(mode)
+    d.scale = float(scale)
+    channels = list(channels)
+    d.n_channels = len(channels)
+    for i, ch in enumerate(channels[:SAMPLE_MAX_CHANNELS]):
+        d.channels[i] = ch if isinstance(ch, SampleChannel) else SampleChannel(int(ch[0]), int(ch[1]), int(ch[2]), 0)
+    d.field = C.c_void_p(int(field_ptr)) if field_ptr else None
+    d.out_stats = C.c_void_p(int(stats_ptr)) if stats_ptr else None
+    return d
+
+
 _lib = None
 
 
@@ -419,6 +459,7 @@ def load_library():
         lib.hnb_effect_import.argtypes = [C.c_void_p, C.POINTER(ImportDesc)]
         lib.hnb_effect_deposit.argtypes = [C.c_void_p, C.POINTER(DepositDesc)]
         lib.hnb_program_deposit.argtypes = [C.c_void_p, C.POINTER(DepositDesc)]
+        lib.hnb_effect_sample.argtypes = [C.c_void_p, C.POINTER(SampleDesc)]
         _lib = lib
     return _lib
 
@@ -856,6 +897,15 @@ class Effect:
         first. Raw device addresses; enqueued on the simulation stream, nothing is read back. As f32: sums.to(torch.float32) * 2.0**-frac_bits."""
         d = deposit_desc(dims, origin, inv_cell, count_ptr, channels, sums_ptr, stats_ptr, accumulate)
         _check(self._lib.hnb_effect_deposit(self._h, C.byref(d)))
+
+    def sample(self, dims, origin, inv_cell, field_ptr, channels, mode=SAMPLE_TRILINEAR, scale=1.0, stats_ptr=None):
+        """hnb_effect_sample: the deposit's way back - for every alive particle inside the uniform grid of export_binned, channel k of the f32 field
+        at field_ptr (device f32[n_cells * len(channels)], channel-minor, 16-byte aligned: a [D, H, W, k] tensor) - its cell's value (SAMPLE_NEAREST)
+        or the trilinear blend of the eight cell centres around it, clamped to the edge (SAMPLE_TRILINEAR) - times `scale` is stored (SAMPLE_SET) or
+        added (SAMPLE_ADD) into channels[k] = (attribute id, component, op). Particles outside the grid and dead slots keep every bit. stats_ptr
+        (device u32[4], optional): visited, sampled, outside, 0. Raw device addresses; enqueued on the simulation stream, nothing is read back."""
+        d = sample_desc(dims, origin, inv_cell, field_ptr, channels, mode, scale, stats_ptr)
+        _check(self._lib.hnb_effect_sample(self._h, C.byref(d)))
 
     def check(self):
         """hnb_effect_check: list permutation, alive bytes, age < lifetime, fault flag - on the device; a dict with "ok"."""
