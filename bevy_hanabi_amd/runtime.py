@@ -42,6 +42,8 @@ ABI_IMPORT_SYMBOLS = ["hnb_effect_import"]
 ABI_DEPOSIT_SYMBOLS = ["hnb_effect_deposit", "hnb_program_deposit"]
 # ... and the one include/hanabi_amd_sample.h declares
 ABI_SAMPLE_SYMBOLS = ["hnb_effect_sample"]
+# ... and the two include/hanabi_amd_splat.h declares
+ABI_SPLAT_SYMBOLS = ["hnb_effect_splat", "hnb_program_splat"]
 
 # hnb_ctx_set_option (include/hanabi_amd.h): name -> option id
 OPTIONS = {"list_order": 1, "alternate": 2, "skip_lists": 3, "age_cohort": 4, "cull_lifetime": 5, "horizon": 6, "transpose": 7, "scene_merge": 8,
@@ -312,6 +314,7 @@ def bounds_desc(attr, dst_ptr, capacity_records):
 
 DEPOSIT_MAX_CHANNELS = 4     # HNB_DEPOSIT_MAX_CHANNELS
 DEPOSIT_ACCUMULATE = 0x1     # HNB_DEPOSIT_ACCUMULATE
+SPLAT_ATTR_ONE = 0xFFFFFFFF  # HNB_SPLAT_ATTR_ONE: a channel of hnb_effect_splat / hnb_program_splat whose value is 1.0f for every particle
 
 
 class DepositChannel(C.Structure):
@@ -460,6 +463,8 @@ def load_library():
         lib.hnb_effect_deposit.argtypes = [C.c_void_p, C.POINTER(DepositDesc)]
         lib.hnb_program_deposit.argtypes = [C.c_void_p, C.POINTER(DepositDesc)]
         lib.hnb_effect_sample.argtypes = [C.c_void_p, C.POINTER(SampleDesc)]
+        lib.hnb_effect_splat.argtypes = [C.c_void_p, C.POINTER(DepositDesc)]
+        lib.hnb_program_splat.argtypes = [C.c_void_p, C.POINTER(DepositDesc)]
         _lib = lib
     return _lib
 
@@ -735,6 +740,11 @@ class Program:
         d = deposit_desc(dims, origin, inv_cell, count_ptr, channels, sums_ptr, stats_ptr, accumulate)
         _check(self._lib.hnb_program_deposit(self._h, C.byref(d)))
 
+    def splat(self, dims, origin, inv_cell, count_ptr, channels=(), sums_ptr=None, stats_ptr=None, accumulate=False):
+        """hnb_program_splat: Effect.splat over every instance of the program, all into the one grid; the stats are the totals."""
+        d = deposit_desc(dims, origin, inv_cell, count_ptr, channels, sums_ptr, stats_ptr, accumulate)
+        _check(self._lib.hnb_program_splat(self._h, C.byref(d)))
+
     def kernel_info(self):
         """Which kernels run this program: 'init=jit|interp|none update=aot-stream:<name>|jit-stream|jit-generic|interp-*'."""
         buf = C.create_string_buffer(4096)
@@ -897,6 +907,15 @@ class Effect:
         first. Raw device addresses; enqueued on the simulation stream, nothing is read back. As f32: sums.to(torch.float32) * 2.0**-frac_bits."""
         d = deposit_desc(dims, origin, inv_cell, count_ptr, channels, sums_ptr, stats_ptr, accumulate)
         _check(self._lib.hnb_effect_deposit(self._h, C.byref(d)))
+
+    def splat(self, dims, origin, inv_cell, count_ptr, channels=(), sums_ptr=None, stats_ptr=None, accumulate=False):
+        """hnb_effect_splat: deposit through the stencil of sample(SAMPLE_TRILINEAR) - the same grid, destinations and fixed-point sums as deposit
+        (and the two may accumulate into one grid); count_ptr takes the particles per OWN cell, unweighted; per channel an inside particle adds
+        round(v * W * 2^frac_bits) to each of the eight cell centres around it, W the corner's trilinear weight, and an outside particle what
+        deposit adds to row n_cells. A channel (SPLAT_ATTR_ONE, 0, frac_bits) has v = 1 for every particle: the weights themselves.
+        stats_ptr (device u32[4], optional): visited, outside, rejected (particle, channel) pairs, 0. Exact to the bit whatever the grouping."""
+        d = deposit_desc(dims, origin, inv_cell, count_ptr, channels, sums_ptr, stats_ptr, accumulate)
+        _check(self._lib.hnb_effect_splat(self._h, C.byref(d)))
 
     def sample(self, dims, origin, inv_cell, field_ptr, channels, mode=SAMPLE_TRILINEAR, scale=1.0, stats_ptr=None):
         """hnb_effect_sample: the deposit's way back - for every alive particle inside the uniform grid of export_binned, channel k of the f32 field
