@@ -44,6 +44,8 @@ ABI_DEPOSIT_SYMBOLS = ["hnb_effect_deposit", "hnb_program_deposit"]
 ABI_SAMPLE_SYMBOLS = ["hnb_effect_sample"]
 # ... and the two include/hanabi_amd_splat.h declares
 ABI_SPLAT_SYMBOLS = ["hnb_effect_splat", "hnb_program_splat"]
+# ... and the one include/hanabi_amd_sample_program.h declares
+ABI_SAMPLE_PROGRAM_SYMBOLS = ["hnb_program_sample"]
 
 # hnb_ctx_set_option (include/hanabi_amd.h): name -> option id
 OPTIONS = {"list_order": 1, "alternate": 2, "skip_lists": 3, "age_cohort": 4, "cull_lifetime": 5, "horizon": 6, "transpose": 7, "scene_merge": 8,
@@ -386,6 +388,29 @@ def sample_desc(dims, origin, inv_cell, field_ptr, channels, mode=SAMPLE_TRILINE
     return d
 
 
+PROGRAM_SAMPLE_MAX_INSTANCES = 65535   # HNB_PROGRAM_SAMPLE_MAX_INSTANCES
+
+
+class ProgramSampleDesc(C.Structure):
+    """HnbProgramSampleDesc (hnb_program_sample): hnb_effect_sample's description, the stride from an instance's field to the next one's and the
+    per-instance stats."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("sample", SampleDesc), ("field_instance_stride", C.c_uint64), ("out_instance_stats", C.c_void_p),
+                ("reserved", C.c_uint64)]
+
+
+def program_sample_desc(dims, origin, inv_cell, field_ptr, channels, mode=SAMPLE_TRILINEAR, scale=1.0, stats_ptr=None, field_instance_stride=0, instance_stats_ptr=None):
+    """sample_desc's arguments - field_ptr: instance 0's field; stats_ptr: the totals - and field_instance_stride: f32 elements from an instance's field
+    to the next one's (0: one field for all); instance_stats_ptr: the device address of n_instances * 4 u32 or None -> ProgramSampleDesc"""
+    d = ProgramSampleDesc()
+    d.struct_size = C.sizeof(ProgramSampleDesc)
+    d.flags = 0
+    d.sample = sample_desc(dims, origin, inv_cell, field_ptr, channels, mode, scale, stats_ptr)
+    d.field_instance_stride = int(field_instance_stride)
+    d.out_instance_stats = C.c_void_p(int(instance_stats_ptr)) if instance_stats_ptr else None
+    d.reserved = 0
+    return d
+
+
 _lib = None
 
 
@@ -465,6 +490,7 @@ def load_library():
         lib.hnb_effect_sample.argtypes = [C.c_void_p, C.POINTER(SampleDesc)]
         lib.hnb_effect_splat.argtypes = [C.c_void_p, C.POINTER(DepositDesc)]
         lib.hnb_program_splat.argtypes = [C.c_void_p, C.POINTER(DepositDesc)]
+        lib.hnb_program_sample.argtypes = [C.c_void_p, C.POINTER(ProgramSampleDesc)]
         _lib = lib
     return _lib
 
@@ -744,6 +770,15 @@ class Program:
         """hnb_program_splat: Effect.splat over every instance of the program, all into the one grid; the stats are the totals."""
         d = deposit_desc(dims, origin, inv_cell, count_ptr, channels, sums_ptr, stats_ptr, accumulate)
         _check(self._lib.hnb_program_splat(self._h, C.byref(d)))
+
+    def sample_all(self, dims, origin, inv_cell, field_ptr, channels, mode=SAMPLE_TRILINEAR, scale=1.0, stats_ptr=None, field_instance_stride=0, instance_stats_ptr=None):
+        """hnb_program_sample: Effect.sample over every instance of the program in one call. field_ptr is instance 0's field; with a
+        field_instance_stride (f32 elements, a multiple of 4, at least n_cells * len(channels)) instance i reads field_ptr + 4 * i * stride bytes,
+        with 0 every instance reads the one field. stats_ptr (device u32[4], optional): the totals; instance_stats_ptr (device u32[n_instances][4],
+        optional): row i = what Effect.sample's stats would hold for instance i. Enqueued on the simulation stream, nothing is read back; the number
+        of enqueues does not depend on the instance count."""
+        d = program_sample_desc(dims, origin, inv_cell, field_ptr, channels, mode, scale, stats_ptr, field_instance_stride, instance_stats_ptr)
+        _check(self._lib.hnb_program_sample(self._h, C.byref(d)))
 
     def kernel_info(self):
         """Which kernels run this program: 'init=jit|interp|none update=aot-stream:<name>|jit-stream|jit-generic|interp-*'."""
