@@ -11,8 +11,10 @@ CPU_SEEDS = list(range(60))
 GPU_SEEDS = list(range(100, 124))
 
 
-def _run(seed, make_runner, abstract=False):
-    asset = random_asset(seed, abstract=abstract)
+def _run(seed, make_runner, abstract=False, capacity=None, frames=random_frames, every=6):
+    """`capacity`, `frames` (seed, capacity -> script) and `every`: tests/test_gpu_option_matrix.py runs the same assets at capacities that fill
+    chunks, compared after every frame."""
+    asset = random_asset(seed, abstract=abstract) if capacity is None else random_asset(seed, capacity, abstract)
     try:
         blob = bh.lower(asset)
     except bh.ShaderGenerateError as e:
@@ -23,11 +25,11 @@ def _run(seed, make_runner, abstract=False):
         import oracle
         o = OracleRunner(asset)
         with pytest.raises(oracle.OracleError):
-            for fr in random_frames(seed, asset.capacity):
+            for fr in frames(seed, asset.capacity):
                 o.step(fr)
         pytest.skip(f"seed {seed}: rejected by both: {e}")
     bh.validate_program(blob)
-    run_script(make_runner(asset), random_frames(seed, asset.capacity), OracleRunner(asset), every=6)
+    run_script(make_runner(asset), frames(seed, asset.capacity), OracleRunner(asset), every=every)
 
 
 @pytest.mark.parametrize("seed", CPU_SEEDS)
@@ -179,9 +181,13 @@ TYPED_CPU_SEEDS = list(range(2000, 2060))
 TYPED_GPU_SEEDS = list(range(2100, 2116))
 
 
-def _run_typed(seed, make_runner, abstract=False):
+def _typed_frames(seed, capacity):
+    return random_frames(seed, capacity, n=24)
+
+
+def _run_typed(seed, make_runner, abstract=False, capacity=None, frames=_typed_frames, every=4):
     from fuzz_assets import random_typed_asset
-    asset = random_typed_asset(seed, abstract=abstract)
+    asset = random_typed_asset(seed, abstract=abstract) if capacity is None else random_typed_asset(seed, capacity, abstract)
     try:
         bh.validate_program(bh.lower(asset))
     except bh.ExprError as e:
@@ -190,10 +196,10 @@ def _run_typed(seed, make_runner, abstract=False):
         import oracle   # an int literal the WGSL would not accept there: the oracle has to refuse the asset too
         o = OracleRunner(asset)
         with pytest.raises(oracle.OracleError):
-            for fr in random_frames(seed, asset.capacity, n=24):
+            for fr in frames(seed, asset.capacity):
                 o.step(fr)
         pytest.skip(f"seed {seed}: rejected by both: {e}")
-    run_script(make_runner(asset), random_frames(seed, asset.capacity, n=24), OracleRunner(asset), every=4)
+    run_script(make_runner(asset), frames(seed, asset.capacity), OracleRunner(asset), every=every)
 
 
 @pytest.mark.parametrize("seed", TYPED_CPU_SEEDS)
