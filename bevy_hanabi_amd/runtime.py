@@ -46,6 +46,8 @@ ABI_SAMPLE_SYMBOLS = ["hnb_effect_sample"]
 ABI_SPLAT_SYMBOLS = ["hnb_effect_splat", "hnb_program_splat"]
 # ... and the one include/hanabi_amd_sample_program.h declares
 ABI_SAMPLE_PROGRAM_SYMBOLS = ["hnb_program_sample"]
+# ... and the one include/hanabi_amd_neighbours.h declares
+ABI_NEIGHBOUR_SYMBOLS = ["hnb_effect_neighbours"]
 
 # hnb_ctx_set_option (include/hanabi_amd.h): name -> option id
 OPTIONS = {"list_order": 1, "alternate": 2, "skip_lists": 3, "age_cohort": 4, "cull_lifetime": 5, "horizon": 6, "transpose": 7, "scene_merge": 8,
@@ -411,6 +413,48 @@ def program_sample_desc(dims, origin, inv_cell, field_ptr, channels, mode=SAMPLE
     return d
 
 
+NEIGHBOUR_MAX_CHANNELS = 4            # HNB_NEIGHBOUR_MAX_CHANNELS
+NEIGHBOUR_MAX_CANDIDATES = 65536      # HNB_NEIGHBOUR_MAX_CANDIDATES
+NEIGHBOUR_W_ONE, NEIGHBOUR_W_U1, NEIGHBOUR_W_U2, NEIGHBOUR_W_U3 = 0, 1, 2, 3   # HNB_NEIGHBOUR_W_*
+NEIGHBOUR_DIFF = 0x1                  # HNB_NEIGHBOUR_DIFF
+
+
+class NeighbourChannel(C.Structure):
+    """HnbNeighbourChannel: the neighbours' `src_comp` of the f32 attribute `src_attr` (or SPLAT_ATTR_ONE), minus the particle's own with
+    NEIGHBOUR_DIFF, weighted and summed in units of 2^-frac_bits, goes into component `dst_comp` of `dst_attr`, stored (SAMPLE_SET) or added."""
+    _fields_ = [("src_attr", C.c_uint32), ("src_comp", C.c_uint32), ("flags", C.c_uint32), ("frac_bits", C.c_uint32), ("dst_attr", C.c_uint32), ("dst_comp", C.c_uint32),
+                ("op", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class NeighbourDesc(C.Structure):
+    """HnbNeighbourDesc (hnb_effect_neighbours): the uniform grid, the radius, the weight, the crowding limit, the scale and the channels."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("dims", C.c_uint32 * 3), ("n_channels", C.c_uint32), ("origin", C.c_float * 3),
+                ("inv_cell", C.c_float * 3), ("radius", C.c_float), ("scale", C.c_float), ("weight", C.c_uint32), ("candidate_limit", C.c_uint32),
+                ("channels", NeighbourChannel * NEIGHBOUR_MAX_CHANNELS), ("out_stats", C.c_void_p)]
+
+
+def neighbour_desc(dims, origin, inv_cell, radius, channels, weight=NEIGHBOUR_W_ONE, candidate_limit=4096, scale=1.0, stats_ptr=None):
+    """dims, origin, inv_cell: export_bins' grid; channels: per channel a (src attribute id, src component, flags, frac_bits, dst attribute id, dst
+    component, op) tuple or a NeighbourChannel; stats_ptr: the device address of 8 u32 or None -> NeighbourDesc. More than NEIGHBOUR_MAX_CHANNELS
+    channels keep their count: the library refuses them."""
+    d = NeighbourDesc()
+    d.struct_size = C.sizeof(NeighbourDesc)
+    d.flags = 0
+    d.dims = (C.c_uint32 * 3)(*[int(x) for x in dims])
+    d.origin = (C.c_float * 3)(*[float(x) for x in origin])
+    d.inv_cell = (C.c_float * 3)(*[float(x) for x in inv_cell])
+    d.radius = float(radius)
+    d.scale = float(scale)
+    d.weight = int(weight)
+    d.candidate_limit = int(candidate_limit)
+    channels = list(channels)
+    d.n_channels = len(channels)
+    for i, ch in enumerate(channels[:NEIGHBOUR_MAX_CHANNELS]):
+        d.channels[i] = ch if isinstance(ch, NeighbourChannel) else NeighbourChannel(*[int(x) for x in ch], 0)
+    d.out_stats = C.c_void_p(int(stats_ptr)) if stats_ptr else None
+    return d
+
+
 _lib = None
 
 
@@ -491,6 +535,7 @@ def load_library():
         lib.hnb_effect_splat.argtypes = [C.c_void_p, C.POINTER(DepositDesc)]
         lib.hnb_program_splat.argtypes = [C.c_void_p, C.POINTER(DepositDesc)]
         lib.hnb_program_sample.argtypes = [C.c_void_p, C.POINTER(ProgramSampleDesc)]
+        lib.hnb_effect_neighbours.argtypes = [C.c_void_p, C.POINTER(NeighbourDesc)]
         _lib = lib
     return _lib
 
@@ -960,6 +1005,16 @@ class Effect:
         (device u32[4], optional): visited, sampled, outside, 0. Raw device addresses; enqueued on the simulation stream, nothing is read back."""
         d = sample_desc(dims, origin, inv_cell, field_ptr, channels, mode, scale, stats_ptr)
         _check(self._lib.hnb_effect_sample(self._h, C.byref(d)))
+
+    def neighbours(self, dims, origin, inv_cell, radius, channels, weight=NEIGHBOUR_W_ONE, candidate_limit=4096, scale=1.0, stats_ptr=None):
+        """hnb_effect_neighbours: particle <-> particle - for every alive particle inside the uniform grid of export_binned, per channel (src attribute
+        id or SPLAT_ATTR_ONE, src component, 0 or NEIGHBOUR_DIFF, frac_bits, dst attribute id, dst component, SAMPLE_SET or SAMPLE_ADD) the
+        fixed-point sum of weight * source over the particles within `radius` (radius * inv_cell <= 1) and within one cell of it, times 2^-frac_bits
+        times scale, stored or added into the destination component. Queries with more than candidate_limit candidates in their 27 cells are left
+        alone and counted. stats_ptr (device u32[8], optional): visited, gathered, outside, crowded, rejected contributions, 0, 0, 0. Raw device
+        addresses; enqueued on the simulation stream, nothing is read back."""
+        d = neighbour_desc(dims, origin, inv_cell, radius, channels, weight, candidate_limit, scale, stats_ptr)
+        _check(self._lib.hnb_effect_neighbours(self._h, C.byref(d)))
 
     def check(self):
         """hnb_effect_check: list permutation, alive bytes, age < lifetime, fault flag - on the device; a dict with "ok"."""
