@@ -405,7 +405,12 @@ int hnb_effect_index(HnbEffect* fx, uint32_t* out_index);
 /* SimulationCondition (src/asset.rs, src/spawn.rs:983-991, src/render/mod.rs:4347-4356): an effect whose asset
  * says WhenVisible is neither ticked nor simulated while it is not visible. The host decides visibility and
  * passes 0 here: the instance is skipped by the following hnb_simulate calls (its state is frozen, its
- * pending spawn request is dropped) until 1 is passed again. Default: simulated. */
+ * pending spawn request is dropped) until 1 is passed again. Default: simulated.
+ * Frozen links (hnb_effect_set_parent): a frozen effect runs neither pass. The event counts of a frozen PARENT
+ * read as 0 to its children from the next frame on - what it emitted in its last simulated frame is still consumed
+ * in the first frozen frame, nothing is consumed twice (the reference clears every child-info row every frame,
+ * whoever is visible: vfx_indirect.wgsl:38-46). A frozen CHILD consumes nothing, and what its parent emits
+ * meanwhile is lost: thawed, it sees the events of the previous frame only. */
 int hnb_effect_set_simulated(HnbEffect* fx, int simulated);
 /* Properties (EffectProperties::set, src/properties.rs:216-395). `n_words` 32-bit words. */
 int hnb_effect_set_property(HnbEffect* fx, const char* name, const void* value, uint32_t n_words);

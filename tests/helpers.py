@@ -277,6 +277,135 @@ def assert_same_system_state(ref, got, what=""):
         assert_same_state(r, g, f"{what} effect #{i}")
 
 
+# ---- linked effects by name: several instances per program, links that change, frozen effects ------------------------
+# (tests/event_scripts.py) Two executors with one interface. The FROZEN rule (hnb_effect_set_simulated(fx, 0); the reference:
+# SimulationCondition::WhenVisible while invisible, src/render/mod.rs:4347-4356 skips both passes, vfx_indirect.wgsl:38-46 clears every
+# child-info row every frame whoever is visible):
+#   - a frozen effect runs neither its init nor its update pass;
+#   - the event counts of a frozen PARENT read as 0 to its children from the next frame on (what it emitted in its last simulated frame
+#     is still consumed in the first frozen frame: the children's init runs before the counts are cleared);
+#   - a frozen CHILD consumes nothing, and what its parent emits meanwhile is lost (a thawed child sees the previous frame only).
+class LinkedOracle:
+    name = "oracle"
+
+    def __init__(self, slot_order=False):
+        self.slot_order, self.fx, self.assets, self.links = slot_order, {}, {}, {}
+
+    def add(self, name, asset):
+        fx = oracle.OracleEffect(bh.serialize_asset(asset))
+        fx.set_list_order(self.slot_order)
+        self.fx[name], self.assets[name] = fx, asset
+
+    def link(self, child, parent, channel, event_capacity):
+        self.fx[child].set_parent(self.fx[parent], channel, event_capacity)
+        self.links[child] = (parent, channel, event_capacity)
+
+    def remove(self, name):
+        assert all(l[0] != name for l in self.links.values()), "unlink or remove the children first: the oracle keeps a pointer to the parent"
+        self.links.pop(name, None)
+        self.fx.pop(name).close()
+        self.assets.pop(name)
+
+    def write_attr(self, name, attr, array):
+        self.fx[name].write_attr(attr.id, array)
+
+    def _level(self, name):
+        return 0 if name not in self.links else 1 + self._level(self.links[name][0])
+
+    def step(self, frames, frozen=()):
+        """frames: {name: Frame} for every effect. Every init pass (parents before children), then every update pass."""
+        assert frames.keys() == self.fx.keys()
+        order = sorted(self.fx, key=self._level)   # (stable: creation order within a level)
+        for n in order:
+            fr = frames[n]
+            if n not in frozen:
+                self.fx[n].init_pass(fr.dt, fr.spawn, fr.seed, time=fr.time, transform=fr.transform)
+        for n in order:
+            fr = frames[n]
+            if n not in frozen:
+                self.fx[n].update_pass(fr.dt, fr.seed, time=fr.time, transform=fr.transform)
+            else:   # the oracle clears its counts inside the update pass only: a fresh link is an empty buffer with count 0
+                for child, (parent, channel, cap) in self.links.items():
+                    if parent == n:
+                        self.fx[child].set_parent(self.fx[n], channel, cap)
+
+    def step_many(self, frames_list, frozen=()):
+        for frames in frames_list:
+            self.step(frames, frozen)
+
+    def state(self):
+        out = {}
+        for n, fx in self.fx.items():
+            out[n] = {"counters": fx.counters(), "alive": fx.alive_list(), "dead": fx.dead_list(),
+                      "attrs": {a.name: fx.read_attr(a.id).view(np.uint32) for a in stored_attrs(self.assets[n])}}
+        return out
+
+
+class LinkedGpu:
+    """`programs`: a dict that outlives the system ({asset key: Program}): effects of one asset are instances of one program."""
+    name = "gpu"
+
+    def __init__(self, ctx, programs=None):
+        self.ctx, self.programs, self.fx, self.assets = ctx, {} if programs is None else programs, {}, {}
+
+    def add(self, name, asset, key=None):
+        key = id(asset) if key is None else key
+        if key not in self.programs:
+            self.programs[key] = self.ctx.create_program(bh.lower(asset))
+        self.fx[name], self.assets[name] = self.programs[key].create_effect(), asset
+
+    def link(self, child, parent, channel, event_capacity):
+        self.fx[child].set_parent(self.fx[parent], channel, event_capacity)
+
+    def remove(self, name):
+        self.fx.pop(name).destroy()
+        self.assets.pop(name)
+
+    def write_attr(self, name, attr, array):
+        self.fx[name].write_attr(attr.id, array)
+
+    def _flags(self, frozen):
+        for n, fx in self.fx.items():
+            fx.set_simulated(n not in frozen)
+
+    def step(self, frames, frozen=()):
+        assert frames.keys() == self.fx.keys()
+        self._flags(frozen)
+        first = next(iter(frames.values()))
+        self.ctx.frame_begin(first.dt, first.time)
+        for n, fr in frames.items():
+            self.fx[n].set_frame(fr.spawn, fr.seed, fr.transform)
+        self.ctx.simulate()
+
+    def step_many(self, frames_list, frozen=()):
+        """The same frames through ONE hnb_simulate_steps call (the flags hold for the whole call)."""
+        self._flags(frozen)
+        for n, fx in self.fx.items():
+            fx.set_frames_ahead([fr[n].spawn for fr in frames_list], [fr[n].seed for fr in frames_list])
+        firsts = [next(iter(fr.values())) for fr in frames_list]
+        self.ctx.simulate_steps([(f.dt, f.time) for f in firsts])
+
+    def state(self):
+        keys = ["capacity", "alive_count", "max_update", "max_spawn", "indirect_write_index", "particle_counter", "instance_count", "dead_count"]
+        out = {}
+        for n, fx in self.fx.items():
+            m = fx.metadata()
+            out[n] = {"counters": {k: m[k] for k in keys}, "alive": fx.alive_list(), "dead": fx.dead_list(),
+                      "attrs": {a.name: fx.read_attr(a.id).view(np.uint32) for a in stored_attrs(self.assets[n])}}
+        return out
+
+    def destroy(self):
+        """every effect of this system; the programs stay with whoever owns the dict"""
+        for n in list(self.fx):
+            self.remove(n)
+
+
+def assert_same_linked_state(ref, got, what=""):
+    assert ref.keys() == got.keys(), (what, sorted(ref), sorted(got))
+    for n in ref:
+        assert_same_state(ref[n], got[n], f"{what} effect '{n}'")
+
+
 # ---- GPU evaluation of the hanabi-math builtins (tests/test_gpu_scale.py, tools/warm_jit_cache.py) -------------
 def math_probe_asset(capacity):
     """One effect whose UPDATE evaluates every transcendental builtin of the expression API on per-particle inputs:

@@ -26,6 +26,8 @@ def main():
         assets += lattice_probe_assets(4096)   # (math_probe_asset among them)
         from test_bounds_abi import trails_vec4
         assets.append(trails_vec4(4096))
+        from event_scripts import warm_assets
+        assets += warm_assets()                 # (tests/test_gpu_event_edges.py)
     except Exception as e:  # tests not present: product programs only
         print("warm_jit_cache: zoo skipped:", e)
     try:
