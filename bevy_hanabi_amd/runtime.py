@@ -48,6 +48,8 @@ ABI_SPLAT_SYMBOLS = ["hnb_effect_splat", "hnb_program_splat"]
 ABI_SAMPLE_PROGRAM_SYMBOLS = ["hnb_program_sample"]
 # ... and the one include/hanabi_amd_neighbours.h declares
 ABI_NEIGHBOUR_SYMBOLS = ["hnb_effect_neighbours"]
+# ... and the one include/hanabi_amd_pairs.h declares
+ABI_PAIRS_SYMBOLS = ["hnb_effect_pairs"]
 
 # hnb_ctx_set_option (include/hanabi_amd.h): name -> option id
 OPTIONS = {"list_order": 1, "alternate": 2, "skip_lists": 3, "age_cohort": 4, "cull_lifetime": 5, "horizon": 6, "transpose": 7, "scene_merge": 8,
@@ -455,6 +457,34 @@ def neighbour_desc(dims, origin, inv_cell, radius, channels, weight=NEIGHBOUR_W_
     return d
 
 
+PAIRS_HALF = 0x1                      # HNB_PAIRS_HALF
+PAIRS_NO_ROW = 0xFFFFFFFF             # HNB_PAIRS_NO_ROW
+
+
+class PairsDesc(C.Structure):
+    """HnbPairsDesc (hnb_effect_pairs): the uniform grid, the radius, the crowding limit and the CSR destinations."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("dims", C.c_uint32 * 3), ("candidate_limit", C.c_uint32), ("origin", C.c_float * 3),
+                ("inv_cell", C.c_float * 3), ("radius", C.c_float), ("pair_capacity", C.c_uint32), ("out_rows", C.c_void_p), ("out_start", C.c_void_p),
+                ("out_pairs", C.c_void_p), ("out_d2", C.c_void_p), ("out_stats", C.c_void_p)]
+
+
+def pairs_desc(dims, origin, inv_cell, radius, rows_ptr, start_ptr, pairs_ptr=None, pair_capacity=0, d2_ptr=None, stats_ptr=None, candidate_limit=4096, half=False):
+    """dims, origin, inv_cell: export_bins' grid; rows_ptr: the device address of capacity u32, start_ptr: of capacity + 1 u32, pairs_ptr / d2_ptr:
+    of pair_capacity u32 / f32 or None, stats_ptr: of 8 u32 or None -> PairsDesc"""
+    d = PairsDesc()
+    d.struct_size = C.sizeof(PairsDesc)
+    d.flags = PAIRS_HALF if half else 0
+    d.dims = (C.c_uint32 * 3)(*[int(x) for x in dims])
+    d.candidate_limit = int(candidate_limit)
+    d.origin = (C.c_float * 3)(*[float(x) for x in origin])
+    d.inv_cell = (C.c_float * 3)(*[float(x) for x in inv_cell])
+    d.radius = float(radius)
+    d.pair_capacity = int(pair_capacity)
+    for name, ptr in (("out_rows", rows_ptr), ("out_start", start_ptr), ("out_pairs", pairs_ptr), ("out_d2", d2_ptr), ("out_stats", stats_ptr)):
+        setattr(d, name, C.c_void_p(int(ptr)) if ptr else None)
+    return d
+
+
 _lib = None
 
 
@@ -536,6 +566,7 @@ def load_library():
         lib.hnb_program_splat.argtypes = [C.c_void_p, C.POINTER(DepositDesc)]
         lib.hnb_program_sample.argtypes = [C.c_void_p, C.POINTER(ProgramSampleDesc)]
         lib.hnb_effect_neighbours.argtypes = [C.c_void_p, C.POINTER(NeighbourDesc)]
+        lib.hnb_effect_pairs.argtypes = [C.c_void_p, C.POINTER(PairsDesc)]
         _lib = lib
     return _lib
 
@@ -1015,6 +1046,18 @@ class Effect:
         addresses; enqueued on the simulation stream, nothing is read back."""
         d = neighbour_desc(dims, origin, inv_cell, radius, channels, weight, candidate_limit, scale, stats_ptr)
         _check(self._lib.hnb_effect_neighbours(self._h, C.byref(d)))
+
+    def pairs(self, dims, origin, inv_cell, radius, rows_ptr, start_ptr, pairs_ptr=None, pair_capacity=0, d2_ptr=None, stats_ptr=None, candidate_limit=4096, half=False):
+        """hnb_effect_pairs: the fixed-radius neighbour list as CSR - for the alive particles inside the uniform grid of export_binned, in its row
+        order: rows_ptr (device u32[capacity]) takes the slot of every row (PAIRS_NO_ROW past the inside rows), start_ptr (device
+        u32[capacity + 1]) the offsets of the runs, pairs_ptr (device u32[pair_capacity]) the slots of the particles within `radius` (radius *
+        inv_cell <= 1) and within one cell of the row's, in ascending row order, d2_ptr (device f32[pair_capacity], optional) their squared
+        distances. half: each pair once, under the lower slot. Only the pairs below pair_capacity are written and the offsets are clamped to it;
+        pair_capacity 0 counts only. Queries with more than candidate_limit candidates list nothing and are counted. stats_ptr (device u32[8],
+        optional): visited, inside, outside, crowded, the true total (low, high word), pairs written, 0. Raw device addresses; enqueued on the
+        simulation stream, nothing is read back and nothing of the effect is written."""
+        d = pairs_desc(dims, origin, inv_cell, radius, rows_ptr, start_ptr, pairs_ptr, pair_capacity, d2_ptr, stats_ptr, candidate_limit, half)
+        _check(self._lib.hnb_effect_pairs(self._h, C.byref(d)))
 
     def check(self):
         """hnb_effect_check: list permutation, alive bytes, age < lifetime, fault flag - on the device; a dict with "ok"."""
