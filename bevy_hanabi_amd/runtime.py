@@ -50,6 +50,8 @@ ABI_SAMPLE_PROGRAM_SYMBOLS = ["hnb_program_sample"]
 ABI_NEIGHBOUR_SYMBOLS = ["hnb_effect_neighbours"]
 # ... and the one include/hanabi_amd_pairs.h declares
 ABI_PAIRS_SYMBOLS = ["hnb_effect_pairs"]
+# ... and the one include/hanabi_amd_neighbours_from.h declares
+ABI_NEIGHBOURS_FROM_SYMBOLS = ["hnb_effect_neighbours_from"]
 
 # hnb_ctx_set_option (include/hanabi_amd.h): name -> option id
 OPTIONS = {"list_order": 1, "alternate": 2, "skip_lists": 3, "age_cohort": 4, "cull_lifetime": 5, "horizon": 6, "transpose": 7, "scene_merge": 8,
@@ -567,6 +569,7 @@ def load_library():
         lib.hnb_program_sample.argtypes = [C.c_void_p, C.POINTER(ProgramSampleDesc)]
         lib.hnb_effect_neighbours.argtypes = [C.c_void_p, C.POINTER(NeighbourDesc)]
         lib.hnb_effect_pairs.argtypes = [C.c_void_p, C.POINTER(PairsDesc)]
+        lib.hnb_effect_neighbours_from.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(NeighbourDesc)]
         _lib = lib
     return _lib
 
@@ -1058,6 +1061,16 @@ class Effect:
         simulation stream, nothing is read back and nothing of the effect is written."""
         d = pairs_desc(dims, origin, inv_cell, radius, rows_ptr, start_ptr, pairs_ptr, pair_capacity, d2_ptr, stats_ptr, candidate_limit, half)
         _check(self._lib.hnb_effect_pairs(self._h, C.byref(d)))
+
+    def neighbours_from(self, source, dims, origin, inv_cell, radius, channels, weight=NEIGHBOUR_W_ONE, candidate_limit=4096, scale=1.0, stats_ptr=None):
+        """hnb_effect_neighbours_from: neighbours() across two effects of one context - the queries are this effect's alive particles, the sources
+        those of the Effect `source`, the destinations planes of this effect. A channel's source attribute is looked up in source's layout (with
+        NEIGHBOUR_DIFF in this effect's as well: v_i is the query's own), its destination in this effect's. There is no self-exclusion; the
+        candidates of a query are sources only. stats_ptr (device u32[8], optional): queries visited, gathered, outside, crowded, rejected
+        contributions, inside sources, alive sources visited, 0. `source` is only read. Raw device addresses; enqueued on the simulation stream,
+        nothing is read back."""
+        d = neighbour_desc(dims, origin, inv_cell, radius, channels, weight, candidate_limit, scale, stats_ptr)
+        _check(self._lib.hnb_effect_neighbours_from(self._h, source._h if source is not None else None, C.byref(d)))
 
     def check(self):
         """hnb_effect_check: list permutation, alive bytes, age < lifetime, fault flag - on the device; a dict with "ok"."""
