@@ -52,6 +52,8 @@ ABI_NEIGHBOUR_SYMBOLS = ["hnb_effect_neighbours"]
 ABI_PAIRS_SYMBOLS = ["hnb_effect_pairs"]
 # ... and the one include/hanabi_amd_neighbours_from.h declares
 ABI_NEIGHBOURS_FROM_SYMBOLS = ["hnb_effect_neighbours_from"]
+# ... and the one include/hanabi_amd_pairs_from.h declares
+ABI_PAIRS_FROM_SYMBOLS = ["hnb_effect_pairs_from"]
 
 # hnb_ctx_set_option (include/hanabi_amd.h): name -> option id
 OPTIONS = {"list_order": 1, "alternate": 2, "skip_lists": 3, "age_cohort": 4, "cull_lifetime": 5, "horizon": 6, "transpose": 7, "scene_merge": 8,
@@ -570,6 +572,7 @@ def load_library():
         lib.hnb_effect_neighbours.argtypes = [C.c_void_p, C.POINTER(NeighbourDesc)]
         lib.hnb_effect_pairs.argtypes = [C.c_void_p, C.POINTER(PairsDesc)]
         lib.hnb_effect_neighbours_from.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(NeighbourDesc)]
+        lib.hnb_effect_pairs_from.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PairsDesc)]
         _lib = lib
     return _lib
 
@@ -1071,6 +1074,17 @@ class Effect:
         nothing is read back."""
         d = neighbour_desc(dims, origin, inv_cell, radius, channels, weight, candidate_limit, scale, stats_ptr)
         _check(self._lib.hnb_effect_neighbours_from(self._h, source._h if source is not None else None, C.byref(d)))
+
+    def pairs_from(self, source, dims, origin, inv_cell, radius, rows_ptr, start_ptr, pairs_ptr=None, pair_capacity=0, d2_ptr=None, stats_ptr=None, candidate_limit=4096):
+        """hnb_effect_pairs_from: pairs() across two effects of one context - the rows are this effect's alive particles inside the grid, in its
+        export_binned order; the runs hold slots of the Effect `source`, in source's export_binned order. rows_ptr (device u32[capacity]) and
+        start_ptr (device u32[capacity + 1]) are sized from THIS effect's capacity; pairs_ptr / d2_ptr (device u32 / f32 [pair_capacity]) take the
+        source slots within `radius` and their squared distances. There is no self-exclusion and no half form; the candidates of a query are
+        sources only. Truncation and pair_capacity 0 as in pairs(). stats_ptr (device u32[8], optional): queries visited, inside, outside,
+        crowded, the true total (low, high word), pairs written, inside sources. Neither effect is written. Raw device addresses; enqueued on
+        the simulation stream, nothing is read back."""
+        d = pairs_desc(dims, origin, inv_cell, radius, rows_ptr, start_ptr, pairs_ptr, pair_capacity, d2_ptr, stats_ptr, candidate_limit, False)
+        _check(self._lib.hnb_effect_pairs_from(self._h, source._h if source is not None else None, C.byref(d)))
 
     def check(self):
         """hnb_effect_check: list permutation, alive bytes, age < lifetime, fault flag - on the device; a dict with "ok"."""
