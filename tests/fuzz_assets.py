@@ -4,6 +4,10 @@ Random float expression trees over the operators of SURVEY.md section 8a row A23
 (scalar / vec2 / vec3 / vec4), assigned to random attributes in init and update, mixed with the stock
 modifiers. Everything stays float so that every generated asset type-checks; integer / bool operators have
 their own zoo assets in test_lowering_cpu.py.
+
+The parameters of the stock modifiers are NOT this module's business: they are fixed and friendly here (a unit circle axis, ConformToSphere
+with radius 1 and no shell or sticky factor, KillAabb with half size 6 and never kill_inside, no SetVelocity*, no Cone3d, no shape in the
+update context). Modifier parameters at their edges are tests/modifier_lattice.py's.
 """
 import numpy as np
 

@@ -552,3 +552,236 @@ def lattice_probe_assets(capacity):
     fns = [math_probe_asset, ieee_probe_asset, ternary_probe_asset, convert_probe_asset, pack_probe_asset, vector_probe_asset]
     fns += [functools.partial(int_probe_asset, which=k) for k in INT_PROBES]
     return [f(capacity) for f in fns] + [uniform_probe_asset(capacity)]
+
+
+# ---- probes of the simulation modifiers (tests/modifier_lattice.py: operands and reference; tests/test_modifier_lattice.py, tests/test_gpu_modifier_lattice.py) --------
+class _PlaneOperands:
+    """parameters read from per-particle attribute planes: vec3 parameters from F32X3_0..3, scalars from the components of F32X4_*, F32X2_*, F32_*; a
+    vec3 that finds no F32X3 left is put together from three scalar lanes. `planes`: {attribute: (n, components) array} to write before the frame."""
+
+    def __init__(self, w, n):
+        self.w, self.n, self.planes = w, n, {}
+        self.vec3s = [A.F32X3_0, A.F32X3_1, A.F32X3_2, A.F32X3_3]
+        self.lanes = [(a, k) for a in (A.F32X4_0, A.F32X4_1, A.F32X4_2, A.F32X4_3) for k in range(4)]
+        self.lanes += [(a, k) for a in (A.F32X2_0, A.F32X2_1, A.F32X2_2, A.F32X2_3) for k in range(2)] + [(a, 0) for a in (A.F32_0, A.F32_1, A.F32_2, A.F32_3)]
+
+    def _lane(self, column):
+        attr, k = self.lanes.pop(0)
+        plane = self.planes.setdefault(attr, np.zeros((self.n, attr.value_type.count), np.float32))
+        plane[:, k] = column
+        e = self.w.attr(attr)
+        return e if attr.value_type.count == 1 else [e.x, e.y, e.z, e.w][k]()
+
+    def operand(self, name, rows):
+        """rows: (n, 3) or (n,)"""
+        if rows.ndim == 2 and self.vec3s:
+            attr = self.vec3s.pop(0)
+            self.planes[attr] = np.ascontiguousarray(rows, np.float32)
+            return self.w.attr(attr)
+        if rows.ndim == 2:
+            x, y, z = (self._lane(rows[:, k]) for k in range(3))
+            return x.vec3(y, z)
+        return self._lane(rows)
+
+
+class _PropertyOperands:
+    """parameters as effect properties: `props[p]`: {name: value} of parameter row p"""
+
+    def __init__(self, w, P):
+        self.w, self.props = w, [dict() for _ in range(P)]
+
+    def operand(self, name, rows):
+        """rows: (P, components)"""
+        vec = rows.shape[1] == 3
+        h = self.w.add_property(name, (0.0, 0.0, 0.0) if vec else 0.0)
+        for p, row in enumerate(rows):
+            self.props[p][name] = np.array(row, np.float32) if vec else np.float32(row[0])
+        return self.w.prop(h)
+
+
+def _modifier_of(op, e):
+    k = op.kind
+    if k == "accel": return bh.AccelModifier(e["accel"])
+    if k == "drag": return bh.LinearDragModifier(e["drag"])
+    if k == "radial": return bh.RadialAccelModifier(e["origin"], e["accel"])
+    if k == "tangent": return bh.TangentAccelModifier(e["origin"], e["axis"], e["accel"])
+    if k == "vel_sphere": return bh.SetVelocitySphereModifier(e["center"], e["speed"])
+    if k == "conform": return bh.ConformToSphereModifier(e["origin"], e["radius"], e["influence"], e["accel"], e["max_speed"], e.get("shell"), e.get("sticky"))
+    if k == "kill_sphere": return bh.KillSphereModifier(e["center"], e["sqr_radius"], op.inside)
+    if k == "kill_aabb": return bh.KillAabbModifier(e["center"], e["half"], op.inside)
+    dim = bh.ShapeDimension.Volume if op.volume else bh.ShapeDimension.Surface
+    if k == "pos_circle": return bh.SetPositionCircleModifier(e["center"], e["axis"], e["radius"], dim)
+    if k == "pos_sphere": return bh.SetPositionSphereModifier(e["center"], e["radius"], dim)
+    raise KeyError(k)
+
+
+def modifier_probe_asset(table, form, order=None):
+    """One effect whose UPDATE is the modifier stack of a modifier_lattice.Table. form "props": every parameter an effect property (uniform operands: the
+    streaming kernels; the stacks of modifier_lattice.AOT match a pre-built sequence exactly); form "planes": every parameter read from a per-particle
+    attribute plane (the generic kernel). order: a permutation of the stack (another order of the same modifiers has no pre-built sequence).
+    Returns (asset, operands): operands.props (per parameter row) or operands.planes (per attribute)."""
+    w = bh.ExprWriter()
+    n = table.Q if form == "props" else table.n
+    src = _PropertyOperands(w, table.P) if form == "props" else _PlaneOperands(w, n)
+    mods = []
+    for i, op in enumerate(table.ops):
+        e = {}
+        for name, p in op.params.items():
+            rows = p if form == "props" else table.param(op, name)
+            e[name] = src.operand(f"m{i}_{name}", rows).expr()
+        mods.append(_modifier_of(op, e))
+    if order is not None:
+        mods = [mods[k] for k in order]
+    inits = [bh.SetAttributeModifier(A.POSITION, w.lit((0.0, 0.0, 0.0)).expr())] + ([] if table.no_motion else [bh.SetAttributeModifier(A.VELOCITY, w.lit((0.0, 0.0, 0.0)).expr())])
+    inits += [bh.SetAttributeModifier(A.AGE, w.lit(0.0).expr()), bh.SetAttributeModifier(A.LIFETIME, w.lit(1e9).expr())]
+    asset = bh.EffectAsset(n, bh.SpawnerSettings.once(float(n)), w.finish())
+    for m in inits:
+        asset.init(m)
+    for m in mods:
+        asset.update(m)
+    return asset, src
+
+
+def init_probe_asset(table):
+    """One effect whose INIT is a position modifier, then a velocity modifier of a modifier_lattice.InitTable, every parameter an effect property; the
+    results are stored right behind them: F32X3_0 = position, F32X3_1 = velocity. Returns (asset, props per parameter row)."""
+    w = bh.ExprWriter()
+    props = [dict() for _ in range(table.P)]
+
+    def operands(tag, params):
+        e = {}
+        for name, rows in params.items():
+            rows = np.asarray(rows, np.float32).reshape(table.P, -1)
+            vec = rows.shape[1] == 3
+            h = w.add_property(f"{tag}_{name}", (0.0, 0.0, 0.0) if vec else 0.0)
+            for p, row in enumerate(rows):
+                props[p][f"{tag}_{name}"] = np.array(row, np.float32) if vec else np.float32(row[0])
+            e[name] = w.prop(h).expr()
+        return e
+    kind, params, volume = table.pos
+    e = operands("p", params)
+    dim = bh.ShapeDimension.Volume if volume else bh.ShapeDimension.Surface
+    pos = {"pos_sphere": lambda: bh.SetPositionSphereModifier(e["center"], e["radius"], dim), "pos_circle": lambda: bh.SetPositionCircleModifier(e["center"], e["axis"], e["radius"], dim),
+           "cone3d": lambda: bh.SetPositionCone3dModifier(e["height"], e["base_radius"], e["top_radius"], dim)}[kind]()
+    kind, params, _ = table.vel
+    v = operands("v", params)
+    vel = {"vel_sphere": lambda: bh.SetVelocitySphereModifier(v["center"], v["speed"]), "vel_circle": lambda: bh.SetVelocityCircleModifier(v["center"], v["axis"], v["speed"]),
+           "vel_tangent": lambda: bh.SetVelocityTangentModifier(v["origin"], v["axis"], v["speed"])}[kind]()
+    inits = [pos, vel, bh.SetAttributeModifier(A.F32X3_0, w.attr(A.POSITION).expr()), bh.SetAttributeModifier(A.F32X3_1, w.attr(A.VELOCITY).expr()),
+             bh.SetAttributeModifier(A.AGE, w.lit(0.0).expr()), bh.SetAttributeModifier(A.LIFETIME, w.lit(1e9).expr())]
+    asset = bh.EffectAsset(table.Q, bh.SpawnerSettings.once(float(table.Q)), w.finish())
+    for m in inits:
+        asset.init(m)
+    return asset, props
+
+
+def run_init_table(group, table, props):
+    """one frame that spawns every particle of every effect of the group (one per parameter row, its properties and its emitter transform set)"""
+    group.step([Frame(1 / 60, table.Q, table.seed, transform=table.xf[i], props=props[i]) for i in range(table.P)])
+    return group.states()
+
+
+class RunnerGroup:
+    """several independent effects of one asset on a CPU executor (OracleRunner, CpuVmRunner), with GpuGroup's interface"""
+
+    def __init__(self, cls, asset_fn, count, **kw):
+        self.runners = [cls(asset_fn(), **kw) for _ in range(count)]
+
+    def step(self, frames):
+        for r, fr in zip(self.runners, frames):
+            r.step(fr)
+
+    def write_attr(self, i, attr, plane):
+        r = self.runners[i]
+        (r.write_attr if hasattr(r, "write_attr") else r.fx.write_attr)(attr.id, plane)
+
+    def states(self):
+        return [r.state() for r in self.runners]
+
+    def close(self):
+        self.runners = []
+
+
+class GpuGroup:
+    """`count` instances of ONE program in one context, stepped by the same frames (properties per instance)"""
+
+    def __init__(self, asset, count, ctx):
+        self.asset, self.ctx = asset, ctx
+        self.prog = ctx.create_program(bh.lower(asset))
+        self.fx = [self.prog.create_effect() for _ in range(count)]
+
+    def step(self, frames):
+        self.ctx.frame_begin(frames[0].dt, frames[0].time)
+        for fx, fr in zip(self.fx, frames):
+            for k, v in fr.props.items():
+                fx.set_property(k, v)
+            fx.set_frame(fr.spawn, fr.seed, fr.transform)
+        self.ctx.simulate()
+
+    def write_attr(self, i, attr, plane):
+        self.fx[i].write_attr(attr.id, plane)
+
+    def states(self):
+        keys = ["capacity", "alive_count", "max_update", "max_spawn", "indirect_write_index", "particle_counter", "instance_count", "dead_count"]
+        out = []
+        for fx in self.fx:
+            m = fx.metadata()
+            out.append({"counters": {k: m[k] for k in keys}, "alive": fx.alive_list(), "dead": fx.dead_list(),
+                        "attrs": {a.name: fx.read_attr(a.id).view(np.uint32) for a in stored_attrs(self.asset)}})
+        return out
+
+
+def run_modifier_table(group, table, form, operands):
+    """spawn every particle (one frame), write the particle planes (and the parameter planes), one update frame of the table's dt and seed with the
+    parameter row's properties: the state of every effect of the group (one for "planes", one per parameter row for "props")"""
+    count = 1 if form == "planes" else table.P
+    m = table.n if form == "planes" else table.Q
+    group.step([Frame(1 / 60, m, 1) for _ in range(count)])
+    for i in range(count):
+        get = (lambda what: table.particle(what)) if form == "planes" else (lambda what: getattr(table, what))
+        if not table.no_motion:
+            group.write_attr(i, A.POSITION, np.ascontiguousarray(get("pos")))
+            group.write_attr(i, A.VELOCITY, np.ascontiguousarray(get("vel")))
+        group.write_attr(i, A.AGE, np.ascontiguousarray(get("age")))
+        group.write_attr(i, A.LIFETIME, np.ascontiguousarray(get("lifetime")))
+        if form == "planes":
+            for attr, plane in operands.planes.items():
+                group.write_attr(i, attr, plane)
+    group.step([Frame(float(table.dt), 0, table.seed, time=1 / 60, props=operands.props[i] if form == "props" else {}) for i in range(count)])
+    return group.states()
+
+
+AGE_LATTICE_ASSETS = ("age", "age_euler", "drag_accel", "age_render")
+
+
+def age_lattice_asset(which, capacity):
+    """The assets of the age / lifetime lattice (modifier_lattice.age_lifetime_planes): "age": one AGE_TICK (ProgAge and the age kernel), "age_euler",
+    "drag_accel" (the headline's stack), "age_render": age_euler with a render modifier that reads AGE (the runtime keeps the plane current)."""
+    w = bh.ExprWriter()
+    inits = [bh.SetAttributeModifier(A.POSITION, w.lit((0.0, 0.0, 0.0)).expr())]
+    if which != "age":
+        inits.append(bh.SetAttributeModifier(A.VELOCITY, w.lit((1.0, 2.0, -0.5)).expr()))
+    inits += [bh.SetAttributeModifier(A.AGE, w.lit(0.0).expr()), bh.SetAttributeModifier(A.LIFETIME, w.lit(1.0).expr())]
+    updates = [bh.LinearDragModifier(w.lit(0.5).expr()), bh.AccelModifier(w.lit((0.0, -3.0, 0.0)).expr())] if which == "drag_accel" else []
+    asset = bh.EffectAsset(capacity, bh.SpawnerSettings.once(float(capacity)), w.finish())
+    for m in inits:
+        asset.init(m)
+    for m in updates:
+        asset.update(m)
+    if which == "age_render":
+        asset.render(bh.ColorOverLifetimeModifier())
+    return asset
+
+
+def modifier_probe_assets():
+    """every probe of tests/test_modifier_lattice.py and tests/test_gpu_modifier_lattice.py (tools/warm_jit_cache.py compiles their kernels ahead of the tests)"""
+    import modifier_lattice as mdl
+    out = []
+    for t in mdl.tables().values():
+        out += [modifier_probe_asset(t, form)[0] for form in ("props", "planes")]
+    ff = mdl.tables()["force_field"]
+    out.append(modifier_probe_asset(ff, "props", order=list(range(len(ff.ops)))[::-1])[0])
+    out += [modifier_probe_asset(mdl.big_table(name), "props")[0] for name in mdl.BIG_STACKS]
+    out += [age_lattice_asset(which, mdl.AGE_CAPACITY) for which in AGE_LATTICE_ASSETS]
+    out += [init_probe_asset(t)[0] for t in mdl.init_tables().values()]
+    return out

@@ -24,6 +24,8 @@ def main():
         assets += [ZOO[k]() for k in sorted(ZOO)]
         from helpers import lattice_probe_assets
         assets += lattice_probe_assets(4096)   # (math_probe_asset among them)
+        from helpers import modifier_probe_assets
+        assets += modifier_probe_assets()      # (tests/test_gpu_modifier_lattice.py)
         from test_bounds_abi import trails_vec4
         assets.append(trails_vec4(4096))
         from event_scripts import warm_assets
